@@ -10,6 +10,11 @@ Launch (driver contract):
   python bench.py --gpus 1 --steps K --warmup W            # single GPU/CPU
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints one JSON result
+line. --dump-outputs DIR additionally writes what the last timed step
+computed (see dump_outputs) so two builds can be compared output for output;
+--full is where any measurement beyond the headline figure goes.
 """
 from __future__ import annotations
 
@@ -59,7 +64,66 @@ def build_model(args, device):
     kwargs.update(getattr(args, 'model_kwargs', {}))
     with torch.device(device):
         model = SE3Transformer(**kwargs)
+    # The library's default init is not variance-preserving at the headline
+    # width: with it the untrained model puts out values of ~1e5 (loss 1.4e9,
+    # gradients up to 1e12), the first SGD update sends every weight to NaN,
+    # and even where it does not, the saturated attention turns a one-ulp
+    # change of a weight into an O(1) change of the output, so no two runs
+    # agree. Halving the weight matrices brings the output to O(1) (loss 1.4,
+    # gradient norm ~1.6): the steps then run on ordinary finite numbers and
+    # repeat from run to run up to bf16 rounding. Same kernels, same shapes.
+    scale = getattr(args, 'init_scale', 1.0)
+    if scale != 1.0:
+        with torch.no_grad():
+            for p_ in model.parameters():
+                if p_.dim() >= 2:
+                    p_.mul_(scale)
     return model
+
+
+GRAD_SAMPLE = 4096          # gradient elements kept per parameter tensor
+DUMP_LIMIT = 64 << 20       # bytes, all dumped arrays together
+
+
+def dump_outputs(dirname, last, model):
+    """Write what the last timed step handed back as DIR/<name>.npy (float32):
+    `loss`, `out` (the model output) and `grad_sample`, the concatenation over
+    model.parameters() of each gradient flattened — whole when it has at most
+    GRAD_SAMPLE elements, otherwise GRAD_SAMPLE of them at indices drawn from
+    a fixed seed. Same arguments -> same indices and same array layout, so
+    two builds compare element for element."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    g = torch.Generator(device='cpu').manual_seed(4321)
+
+    def sample(t, limit):
+        flat = t.detach().reshape(-1)
+        if flat.numel() > limit:
+            idx = torch.randint(0, flat.numel(), (limit,), generator=g)
+            flat = flat[idx.to(flat.device)]
+        return flat.float().cpu().numpy()
+
+    with_grad = [p_ for p_ in model.parameters() if p_.grad is not None]
+    # the gradient sample takes at most half of the limit
+    per = min(GRAD_SAMPLE, max(DUMP_LIMIT // 8 // max(len(with_grad), 1), 1))
+    grads = [sample(p_.grad, per) for p_ in with_grad]
+    arrays = {
+        'loss': last['loss'].detach().float().reshape(1).cpu().numpy(),
+        'grad_sample': np.concatenate(grads) if grads
+        else np.zeros(0, dtype=np.float32),
+    }
+    # the output is small at every shipped config; sample it only if a custom
+    # shape would push the dump past the limit
+    room = DUMP_LIMIT - sum(a.nbytes for a in arrays.values())
+    arrays['out'] = sample(last['out'], max(room // 4, 1))
+    if last['out'].numel() * 4 <= room:
+        arrays['out'] = arrays['out'].reshape(last['out'].shape)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + '.npy'), a)
+        if not np.isfinite(a).all():
+            print(f'[bench] dumped {name} holds non-finite values (the run '
+                  'diverged; try a smaller --lr)',
+                  file=sys.stderr, flush=True)
 
 
 def main():
@@ -89,6 +153,11 @@ def main():
                    help='DP gradient all-reduce dtype (bf16 halves xGMI '
                         'traffic; see parallel/ddp.py for the error bound)')
     p.add_argument('--optimizer', default='sgd', choices=['sgd', 'adam'])
+    p.add_argument('--lr', type=float, default=1e-4,
+                   help='optimizer step size')
+    p.add_argument('--init-scale', type=float, default=0.5,
+                   help='factor applied to every weight matrix after the '
+                        'default init (see build_model)')
     p.add_argument('--zero1', action='store_true',
                    help='shard optimizer state across ranks (ZeRO-1, '
                         'parallel/zero.py). At the 18.2B-param headline '
@@ -96,6 +165,16 @@ def main():
                         'sharded across multiple GPUs.')
     p.add_argument('--preset', default=None, choices=sorted(PRESETS),
                    help='one of the BASELINE.json named configs')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='after the timed steps write what the last step '
+                        'computed (loss, model output, a fixed seeded sample '
+                        'of every parameter gradient) as DIR/<name>.npy')
+    p.add_argument('--full', action='store_true',
+                   help='also run the measurements and checks beyond the '
+                        'headline figure. A plain run already does only what '
+                        'the headline needs (set up, warm up, time the '
+                        'steps), so today this adds nothing; anything extra '
+                        'added later belongs behind it.')
     args = p.parse_args()
     args.model_kwargs = {}
     if args.preset:
@@ -126,7 +205,7 @@ def main():
 
     optim_cls = torch.optim.AdamW if args.optimizer == 'adam' \
         else torch.optim.SGD
-    opt_kwargs = dict(lr=1e-4)
+    opt_kwargs = dict(lr=args.lr)
     will_graph = (args.graph if args.graph is not None else world == 1) \
         and use_cuda
     if args.optimizer == 'adam' and will_graph:
@@ -159,6 +238,8 @@ def main():
     if args.timers and use_cuda:
         phase_events = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
 
+    last = {}
+
     def train_step():
         if ddp is not None:
             ddp.zero_grad_buffers()
@@ -180,6 +261,10 @@ def main():
         opt.step()
         if phase_events:
             phase_events[3].record()
+        # what a caller of the step receives; under hipGraph replay these are
+        # the graph's static tensors, refreshed by every replay. Detached:
+        # a kept autograd graph would outlive the step and break capture.
+        last['loss'], last['out'] = loss.detach(), out.detach()
         return loss
 
     def report_phases(tag):
@@ -254,6 +339,9 @@ def main():
     ms_per_step = elapsed / args.steps * 1000.
     samples_per_sec = (args.batch * world * args.steps) / elapsed
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, model)
+
     if rank == 0:
         metric = 'train samples/sec (fwd+bwd), 1024-pt dim=512 depth=6 num_degrees=4'
         if args.preset:
@@ -279,6 +367,7 @@ def main():
                 'global_batch': args.batch * world,
                 'parallelism': f'dp{world}',
                 'n_params': n_params,
+                'init_scale': args.init_scale,
                 'optimizer': args.optimizer + ('+zero1' if args.zero1 else ''),
                 'preset': args.preset,
                 'hipgraph': graph_captured,

@@ -34,6 +34,33 @@ def test_bench_single_process():
     assert d['n_gpus'] == 1
 
 
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs writes the last step's loss, model output and gradient
+    sample as float32 .npy files; the same arguments give the same inputs and
+    the same sample layout on every run, and --full leaves the headline path
+    untouched. CPU so that the arithmetic itself is run-to-run exact."""
+    import numpy as np
+    env = dict(os.environ, HIP_VISIBLE_DEVICES='', CUDA_VISIBLE_DEVICES='')
+    dumps = []
+    for name, extra in (('a', []), ('b', ['--full'])):
+        d = tmp_path / name
+        r = subprocess.run([sys.executable, 'bench.py', '--gpus', '1'] + TINY
+                           + ['--steps', '2', '--dump-outputs', str(d)] + extra,
+                           capture_output=True, text=True, cwd=REPO,
+                           timeout=600, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert _check_line(r.stdout)['steps'] == 2
+        dumps.append({f.name: np.load(f) for f in sorted(d.iterdir())})
+    a, b = dumps
+    assert set(a) == set(b) == {'loss.npy', 'out.npy', 'grad_sample.npy'}
+    assert a['out.npy'].shape == (1, 32, 32) and a['loss.npy'].shape == (1,)
+    assert a['grad_sample.npy'].size > 0 and a['grad_sample.npy'].any()
+    for k in a:
+        assert a[k].dtype == np.float32 and np.isfinite(a[k]).all()
+        assert sum(v.nbytes for v in a.values()) <= 64 << 20
+        assert np.array_equal(a[k], b[k]), k
+
+
 def test_bench_two_process_gloo():
     # hide any GPU so setup_distributed picks gloo: two ranks cannot share
     # one device over nccl (this test exercises the CPU DP path everywhere)
@@ -149,12 +176,16 @@ def test_bench_preset_with_explicit_override():
     assert d['metric'].endswith('preset=qm9')
 
 
-def test_serve_loads_checkpoint(tmp_path):
+def test_serve_loads_checkpoint(tmp_path, monkeypatch):
     """serve.py --checkpoint actually loads the weights: predictions from a
     server started on a saved checkpoint differ from random init and equal
     a direct forward of the checkpointed model."""
     import importlib.util
     import torch
+    # the comparison below is against an fp32 CPU forward at atol=1e-5, so
+    # the server must take its CPU path too, also where a GPU is present
+    # (there it would otherwise answer from the bf16 autocast path)
+    monkeypatch.setattr(torch.cuda, 'is_available', lambda: False)
     spec = importlib.util.spec_from_file_location(
         'serve_example2', os.path.join(REPO, 'examples', 'serve.py'))
     serve = importlib.util.module_from_spec(spec)
