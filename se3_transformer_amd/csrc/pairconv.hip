@@ -471,6 +471,11 @@ void ubuild_fwd(torch::Tensor B, torch::Tensor X, torch::Tensor Ut,
                 int64_t O, int64_t I, int64_t F);
 void ubuild_bwd_dx(torch::Tensor B, torch::Tensor dU, torch::Tensor dX,
                    int64_t O, int64_t I, int64_t F);
+void ubuild_bwd_db(torch::Tensor X, torch::Tensor dU, torch::Tensor dB,
+                   int64_t O, int64_t I, int64_t F);
+void sh_basis_bwd(torch::Tensor rel, torch::Tensor qcat, torch::Tensor normtab,
+                  torch::Tensor meta, torch::Tensor dK, torch::Tensor drel,
+                  int64_t L);
 void egnn_rel_dist_fwd(torch::Tensor ht, torch::Tensor idx, torch::Tensor dist);
 void egnn_rel_dist_bwd(torch::Tensor ht, torch::Tensor idx, torch::Tensor gdist,
                        torch::Tensor dht);
@@ -515,6 +520,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("ubuild_fwd", &ubuild_fwd,
           "basis x features precontraction (e-contiguous out)");
     m.def("ubuild_bwd_dx", &ubuild_bwd_dx, "ubuild dX backward");
+    m.def("ubuild_bwd_db", &ubuild_bwd_db,
+          "ubuild dB backward (differentiable coordinates)");
+    m.def("sh_basis_bwd", &sh_basis_bwd,
+          "fused spherical-harmonics + basis backward: dK -> d rel");
     m.def("egnn_rel_dist_fwd", &egnn_rel_dist_fwd,
           "EGNN neighbor rel-htype distances (no n^2 intermediate)");
     m.def("egnn_rel_dist_bwd", &egnn_rel_dist_bwd, "its backward");

@@ -9,10 +9,17 @@
 //
 // Convention parity with ops/sh.py (reference basis.py:57-95, irr_repr.py:103):
 //   x_sh, y_sh, z_sh = z, x, y; ct = -z_sh/r; st = rho/r; cp = x_sh/rho; sp = y_sh/rho.
+//
+// Backward (differentiable coordinates): sh_basis_bwd maps the (E, TOT)
+// cotangent of the packed output to d rel (E, 3), one thread per edge with
+// the same LDS column now holding dY; the per-edge math is sh_basis_bwd.h.
+// Each edge owns its row, so there are no atomics.
 
 #include <torch/extension.h>
 #include <hip/hip_runtime.h>
 #include <ATen/hip/HIPContext.h>
+
+#include "sh_basis_bwd.h"
 
 #define NTSH 256
 
@@ -114,4 +121,53 @@ void sh_basis_fwd(torch::Tensor rel, torch::Tensor qcat, torch::Tensor normtab,
                        npairs, out.data_ptr<float>(), E, TOT, (int)L);
     hipError_t err = hipGetLastError();
     TORCH_CHECK(err == hipSuccess, "sh_basis: ", hipGetErrorString(err));
+}
+
+__global__ void __launch_bounds__(NTSH)
+sh_basis_bwd_kernel(const float* __restrict__ rel,     // (E, 3)
+                    const float* __restrict__ qcat,
+                    const float* __restrict__ normtab,
+                    const int* __restrict__ meta,      // npairs x 4
+                    int npairs, const float* __restrict__ dK,  // (E, TOT)
+                    float* __restrict__ drel,          // (E, 3)
+                    int E, int TOT, int L) {
+    extern __shared__ __attribute__((aligned(16))) float y_lds[]; // [(L+1)^2][NTSH]
+    const int tid = threadIdx.x;
+    const int e = blockIdx.x * NTSH + tid;
+    if (e >= E) return;
+    float gx, gy, gz;
+    sh_basis_bwd_edge(rel[(size_t)e * 3], rel[(size_t)e * 3 + 1],
+                      rel[(size_t)e * 3 + 2], qcat, normtab, meta, npairs,
+                      dK + (size_t)e * TOT, y_lds + tid, NTSH, L,
+                      &gx, &gy, &gz);
+    drel[(size_t)e * 3] = gx;
+    drel[(size_t)e * 3 + 1] = gy;
+    drel[(size_t)e * 3 + 2] = gz;
+}
+
+void sh_basis_bwd(torch::Tensor rel, torch::Tensor qcat, torch::Tensor normtab,
+                  torch::Tensor meta, torch::Tensor dK, torch::Tensor drel,
+                  int64_t L) {
+    TORCH_CHECK(rel.is_cuda() && rel.dtype() == torch::kFloat32 && rel.is_contiguous());
+    TORCH_CHECK(dK.is_cuda() && dK.dtype() == torch::kFloat32 && dK.is_contiguous());
+    TORCH_CHECK(drel.is_cuda() && drel.dtype() == torch::kFloat32 && drel.is_contiguous());
+    TORCH_CHECK(qcat.is_contiguous() && normtab.is_contiguous() && meta.is_contiguous());
+    TORCH_CHECK(meta.dtype() == torch::kInt32 && meta.size(1) == 4);
+    int E = rel.size(0);
+    int TOT = dK.size(1);
+    int npairs = meta.size(0);
+    TORCH_CHECK(rel.size(1) == 3 && dK.size(0) == E && drel.size(0) == E &&
+                drel.size(1) == 3);
+    if (E == 0) return;
+    int S = (int)((L + 1) * (L + 1));
+    size_t lds = (size_t)S * NTSH * sizeof(float);
+    auto stream = at::cuda::getCurrentHIPStream();
+    dim3 grid((E + NTSH - 1) / NTSH);
+    hipLaunchKernelGGL(sh_basis_bwd_kernel, grid, dim3(NTSH), lds, stream,
+                       rel.data_ptr<float>(), qcat.data_ptr<float>(),
+                       normtab.data_ptr<float>(), meta.data_ptr<int>(),
+                       npairs, dK.data_ptr<float>(), drel.data_ptr<float>(),
+                       E, TOT, (int)L);
+    hipError_t err = hipGetLastError();
+    TORCH_CHECK(err == hipSuccess, "sh_basis_bwd: ", hipGetErrorString(err));
 }

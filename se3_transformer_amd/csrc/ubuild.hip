@@ -10,9 +10,13 @@
 // by all C channels), output written directly in the e-contiguous layout
 // the pairconv kernels consume.
 //
-// Backward (dX only): dX[e, c, i] = sum_{f,o} B[e,o,i,f] * dU[(c*F+f), o, e].
-// dB (differentiable_coors) stays on the eager path — the Python wrapper
-// gates on basis.requires_grad.
+// Backward:
+//   dX[e, c, i]    = sum_{f,o} B[e,o,i,f] * dU[(c*F+f), o, e]   (always)
+//   dB[e, o, i, f] = sum_c     X[e,c,i]   * dU[(c*F+f), o, e]   (only when the
+// basis requires grad, i.e. differentiable_coors). dB is a sibling kernel
+// rather than a second output of the dX kernel: the dX kernel's LDS already
+// holds B and a dU tile, and adding the fp32 dB tile would pass 64 KiB for
+// the (7,7,7) pair. The price is one extra read of dU on that path only.
 
 #include <torch/extension.h>
 #include <hip/hip_runtime.h>
@@ -140,6 +144,84 @@ ubuild_bwd_dx_kernel(const float* __restrict__ B,   // (E, O, I, F)
     }
 }
 
+// dB[e,o,i,f] = sum_c X[e,c,i] * dU[(c*F+f), o, e]. Same 16-edge dU tile as
+// the dX kernel; every thread owns up to UB_DBK fixed (o,i,f,e) outputs and
+// keeps their sums over all channel chunks in registers, so dB is written
+// once and needs no atomics. Straight-through for the forward's bf16
+// rounding of B and X.
+#define UB_DBK 22        // ceil(16 * 343 / 256)
+
+template <typename TX>
+__global__ void __launch_bounds__(UB_NT)
+ubuild_bwd_db_kernel(const TX* __restrict__ X,      // (E, C, I)
+                     const float* __restrict__ dU,  // (C*F, O, E) f32
+                     float* __restrict__ dB,        // (E, O, I, F)
+                     int E, int C, int O, int I, int F) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* g_lds = reinterpret_cast<float*>(smem);            // [8c][F*O][16e]
+    float* x_lds = g_lds + UB_CB * F * O * UB_EB;             // [8c][I][16e]
+
+    const int tid = threadIdx.x;
+    const int e0 = blockIdx.x * UB_EB;
+    const int oif = O * I * F;
+    const int fo = F * O;
+    const int nout = UB_EB * oif;
+
+    // per-output LDS offsets (channel 0), packed: x offset | g offset << 10
+    int offs[UB_DBK];
+    float acc[UB_DBK];
+#pragma unroll
+    for (int k = 0; k < UB_DBK; ++k) {
+        int t = tid + k * UB_NT;
+        int e = t % UB_EB;
+        int r = (t / UB_EB) % oif;     // wraps only for t >= nout (unused)
+        int o = r / (I * F), rem = r % (I * F);
+        int i = rem / F, f = rem % F;
+        offs[k] = (i * UB_EB + e) | (((f * O + o) * UB_EB + e) << 10);
+        acc[k] = 0.f;
+    }
+
+    for (int c0 = 0; c0 < C; c0 += UB_CB) {
+        __syncthreads();
+        for (int t = tid; t < UB_CB * fo * UB_EB; t += UB_NT) {
+            int e = t % UB_EB;
+            int r = t / UB_EB;         // c*F*O + (f*O + o)
+            int c = r / fo, fo_i = r % fo;
+            int f = fo_i / O, o = fo_i % O;
+            g_lds[t] = (e0 + e < E)
+                ? dU[((size_t)((c0 + c) * F + f) * O + o) * E + e0 + e] : 0.f;
+        }
+        for (int t = tid; t < UB_CB * I * UB_EB; t += UB_NT) {
+            int e = t % UB_EB;
+            int r = t / UB_EB;         // c*I + i
+            int c = r / I, i = r % I;
+            x_lds[t] = (e0 + e < E)
+                ? (float)X[((size_t)(e0 + e) * C + c0 + c) * I + i] : 0.f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < UB_DBK; ++k) {
+            if (tid + k * UB_NT < nout) {
+                const float* xp = x_lds + (offs[k] & 1023);
+                const float* gp = g_lds + (offs[k] >> 10);
+                float a = acc[k];
+#pragma unroll
+                for (int c = 0; c < UB_CB; ++c)
+                    a = fmaf(xp[c * I * UB_EB], gp[c * fo * UB_EB], a);
+                acc[k] = a;
+            }
+        }
+    }
+
+#pragma unroll
+    for (int k = 0; k < UB_DBK; ++k) {
+        int t = tid + k * UB_NT;
+        int e = t % UB_EB, r = t / UB_EB;
+        if (t < nout && e0 + e < E)
+            dB[(size_t)(e0 + e) * oif + r] = acc[k];
+    }
+}
+
 void ubuild_fwd(torch::Tensor B, torch::Tensor X, torch::Tensor Ut,
                 int64_t O, int64_t I, int64_t F) {
     TORCH_CHECK(B.is_cuda() && B.is_contiguous() && B.dtype() == torch::kFloat32);
@@ -198,4 +280,39 @@ void ubuild_bwd_dx(torch::Tensor B, torch::Tensor dU, torch::Tensor dX,
     }
     hipError_t err = hipGetLastError();
     TORCH_CHECK(err == hipSuccess, "ubuild_bwd_dx: ", hipGetErrorString(err));
+}
+
+void ubuild_bwd_db(torch::Tensor X, torch::Tensor dU, torch::Tensor dB,
+                   int64_t O, int64_t I, int64_t F) {
+    TORCH_CHECK(X.is_cuda() && X.is_contiguous() && X.dim() == 3);
+    TORCH_CHECK(dU.is_cuda() && dU.is_contiguous() &&
+                dU.dtype() == torch::kFloat32);
+    TORCH_CHECK(dB.is_cuda() && dB.is_contiguous() &&
+                dB.dtype() == torch::kFloat32);
+    int E = X.size(0);
+    int C = X.size(1);
+    TORCH_CHECK(X.size(2) == I && dU.numel() == (int64_t)C * F * O * E &&
+                dB.numel() == (int64_t)E * O * I * F);
+    TORCH_CHECK(C % UB_CB == 0, "channels must be a multiple of 8");
+    TORCH_CHECK(O * I * F <= 343);
+    if (E == 0) return;
+    size_t lds = (size_t)UB_CB * UB_EB * (F * O + I) * 4;
+    TORCH_CHECK(lds <= 64 * 1024, "degree pair too large for LDS staging");
+    auto stream = at::cuda::getCurrentHIPStream();
+    dim3 grid((E + UB_EB - 1) / UB_EB);
+    if (X.dtype() == torch::kFloat32) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(ubuild_bwd_db_kernel<float>), grid,
+                           dim3(UB_NT), lds, stream, X.data_ptr<float>(),
+                           dU.data_ptr<float>(), dB.data_ptr<float>(),
+                           E, C, (int)O, (int)I, (int)F);
+    } else {
+        TORCH_CHECK(X.dtype() == torch::kBFloat16);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(ubuild_bwd_db_kernel<__bf16>), grid,
+                           dim3(UB_NT), lds, stream,
+                           reinterpret_cast<const __bf16*>(X.data_ptr()),
+                           dU.data_ptr<float>(), dB.data_ptr<float>(),
+                           E, C, (int)O, (int)I, (int)F);
+    }
+    hipError_t err = hipGetLastError();
+    TORCH_CHECK(err == hipSuccess, "ubuild_bwd_db: ", hipGetErrorString(err));
 }

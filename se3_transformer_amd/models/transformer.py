@@ -271,7 +271,11 @@ class SE3Transformer(nn.Module):
         assert self.attend_sparse_neighbors or neighbors > 0, \
             'must attend to sparse neighbors or have num_neighbors > 0'
 
-        off_diag = _off_diag_indices(n, device)  # (n, n-1)
+        # (n, n-1) index table: only the adjacency features and the eager
+        # graph build need it; the kNN-kernel path stays free of n^2 tensors
+        off_diag = _off_diag_indices(n, device) \
+            if exists(self.num_adj_degrees) or self.attend_sparse_neighbors \
+            else None
 
         # N-hop adjacency labels
         adj_indices = None
@@ -308,11 +312,13 @@ class SE3Transformer(nn.Module):
         # semantics identical to the eager branch, including neighbor_mask
         # exclusion, sparse-adjacency priority and causal masking. (The
         # eager path's advisory print when neighbor_mask exceeds
-        # `neighbors` is skipped here.)
+        # `neighbors` is skipped here.) Under differentiable_coors the
+        # kernel still does the selection and the geometry is re-derived
+        # from its indices below; f64 coordinates, k > 64 and
+        # SE3_EAGER_KNN=1 stay on the eager branch.
         from ..ops import fused as _fusedmod
         k_total = int(min(neighbors + num_sparse_neighbors, n - 1))  # neighbors may be inf
         use_knn = (coors.is_cuda and coors.dtype == torch.float32
-                   and not self.differentiable_coors
                    and 1 <= k_total <= 64
                    and os.environ.get('SE3_EAGER_KNN') != '1'
                    and _fusedmod.ext_available())
@@ -345,6 +351,19 @@ class SE3Transformer(nn.Module):
             neighbor_rel_pos = relp
             neighbor_mask = nm.bool()
 
+            if self.differentiable_coors and coors.requires_grad \
+                    and torch.is_grad_enabled():
+                # the selection (idx, mask) is discrete and carries no
+                # gradient; the geometry is re-derived from the kept indices
+                # with differentiable O(n*k) gathers. Slots the kernel
+                # fabricated (no candidate; dist == 0) keep its constant
+                # zero geometry.
+                real = dist > 0
+                rel = coors.unsqueeze(2) - batched_index_select(coors, idx, dim=1)
+                neighbor_rel_pos = torch.where(real.unsqueeze(-1), rel, relp)
+                neighbor_rel_dist = torch.where(
+                    real, neighbor_rel_pos.norm(dim=-1), dist)
+
             if exists(edges) and exists(self.edge_emb):
                 edges = self.edge_emb(edges)
             if exists(edges):
@@ -361,6 +380,8 @@ class SE3Transformer(nn.Module):
                     else adj_e
         else:
             # relative geometry (self excluded by indexing, not masked_select)
+            if off_diag is None:
+                off_diag = _off_diag_indices(n, device)
             indices = off_diag.unsqueeze(0).expand(b, n, n - 1)
             rel_pos_full = coors.unsqueeze(2) - coors.unsqueeze(1)  # b i j 3
             rel_pos = _remove_self(rel_pos_full, off_diag)          # b i j-1 3

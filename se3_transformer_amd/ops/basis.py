@@ -9,7 +9,8 @@ changes for the MI355X build:
   computes bit-identical tables on CPU float64.
 * ``differentiable=True`` genuinely keeps the autograd graph through the
   spherical harmonics (the reference's flag is inverted/defeated:
-  basis.py:171 vs :200-203).
+  basis.py:171 vs :200-203). On CUDA fp32 the packed layout does so through
+  the HIP backward of the fused kernel (``_ShBasisFn``, first order).
 * Spherical harmonics for all J are evaluated in ONE vectorized pass straight
   from cartesian offsets (no per-(l,m) recursion / global cache) — the same
   structure as the fused HIP basis kernel.
@@ -248,30 +249,71 @@ def _build_sh_tables(key, max_degree, device):
     return tables
 
 
+class _ShBasisFn(torch.autograd.Function):
+    """Fused SH + basis kernel with its HIP backward (csrc/sh_basis.hip):
+    rel (E,3) fp32 -> packed basis (E,TOT) fp32, and dK -> d rel. First order
+    only; second-order gradients need the eager path (SE3_EAGER_BASIS=1)."""
+
+    @staticmethod
+    def forward(ctx, rel, qcat, normtab, meta, TOT, L):
+        from . import fused as _fused
+        out = torch.empty(rel.shape[0], TOT, dtype=torch.float32, device=rel.device)
+        _fused._EXT.sh_basis_fwd(rel, qcat, normtab, meta, out, L)
+        ctx.save_for_backward(rel, qcat, normtab, meta)
+        ctx.L = L
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dK):
+        from . import fused as _fused
+        rel, qcat, normtab, meta = ctx.saved_tensors
+        drel = torch.empty_like(rel)
+        _fused._EXT.sh_basis_bwd(rel, qcat, normtab, meta,
+                                 dK.contiguous().float(), drel, ctx.L)
+        return drel, None, None, None, None, None
+
+
 def get_basis_packed(r_ij: torch.Tensor, max_degree: int, differentiable: bool = False):
     """Compact per-pair basis for the fused conv path.
 
     Returns {(d_in, d_out): tensor [..., 2*d_out+1, 2*d_in+1, F]} with
     F = 2*min(d_in,d_out)+1, contiguous, no broadcast singleton dims.
 
-    On CUDA fp32 non-differentiable inputs this runs the fused HIP
-    spherical-harmonics + basis kernel (csrc/sh_basis.hip) in one launch.
+    On CUDA fp32 inputs this runs the fused HIP spherical-harmonics + basis
+    kernel (csrc/sh_basis.hip) in one launch; with ``differentiable=True``
+    the result carries a first-order autograd edge to ``r_ij`` through the
+    kernel's HIP backward. ``differentiable=False`` returns a detached
+    tensor. float64 inputs, CPU tensors and SE3_EAGER_BASIS=1 take the eager
+    path (which also supports double backward).
     """
     device, dtype = r_ij.device, r_ij.dtype
 
-    if (r_ij.is_cuda and not differentiable and dtype == torch.float32
+    if (r_ij.is_cuda and dtype == torch.float32
             and os.environ.get('SE3_EAGER_BASIS') != '1'):
         from . import fused as _fused
         if _fused.ext_available():
             qcat, normtab, meta, TOT, layout = _sh_basis_tables(max_degree, device)
             rel = r_ij.reshape(-1, 3).contiguous()
             E = rel.shape[0]
-            out = torch.empty(E, TOT, dtype=torch.float32, device=device)
-            _fused._EXT.sh_basis_fwd(rel, qcat, normtab, meta, out, 2 * max_degree)
+            if differentiable and rel.requires_grad and torch.is_grad_enabled():
+                if not hasattr(_fused._EXT, 'sh_basis_bwd'):
+                    raise RuntimeError(
+                        'se3_transformer_amd._C lacks sh_basis_bwd; rebuild '
+                        'the extension (python scripts/build_ext.py)')
+                out = _ShBasisFn.apply(rel, qcat, normtab, meta, TOT,
+                                       2 * max_degree)
+            else:
+                out = torch.empty(E, TOT, dtype=torch.float32, device=device)
+                _fused._EXT.sh_basis_fwd(rel.detach(), qcat, normtab, meta,
+                                         out, 2 * max_degree)
+            # layout offsets are consecutive: one split (a single cat in
+            # backward) instead of per-pair slices (one padded E x TOT
+            # gradient each)
+            parts = out.split([O * I * F for _, O, I, F in layout.values()], dim=1)
             basis = {}
-            for (d_in, d_out), (off, O, I, F) in layout.items():
-                basis[(d_in, d_out)] = out[:, off:off + O * I * F] \
-                    .reshape(*r_ij.shape[:-1], O, I, F)
+            for (pair, (off, O, I, F)), part in zip(layout.items(), parts):
+                basis[pair] = part.reshape(*r_ij.shape[:-1], O, I, F)
             return basis
     y_packed = _compute_sh(r_ij, 2 * max_degree, differentiable)
 

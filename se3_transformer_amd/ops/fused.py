@@ -302,33 +302,52 @@ def fused_attention(q, k, v, mask_u8, n, heads, scale, kv_one=False,
 class _UBuildFn(torch.autograd.Function):
     """Basis-feature precontraction (csrc/ubuild.hip):
     Ut[(c f), o, e] = sum_i B[e,o,i,f] x[e,c,i], emitted directly in the
-    e-contiguous layout the pairconv kernels consume. dB is not produced
-    (the caller gates on basis.requires_grad)."""
+    e-contiguous layout the pairconv kernels consume. When the basis
+    requires grad (differentiable_coors) x is saved too and backward also
+    returns dB[e,o,i,f] = sum_c x[e,c,i] dUt[(c f),o,e] in fp32,
+    straight-through for the forward's bf16 rounding. First order only."""
 
     @staticmethod
     def forward(ctx, x, B, O, I, F):
         ext = _load_ext()
         E, C, _ = x.shape
         Ut = torch.empty(C * F, O, E, dtype=torch.bfloat16, device=x.device)
-        ext.ubuild_fwd(B, x.contiguous(), Ut, O, I, F)
-        ctx.save_for_backward(B)
+        xc = x.contiguous()
+        ext.ubuild_fwd(B, xc, Ut, O, I, F)
+        if ctx.needs_input_grad[1]:
+            ctx.save_for_backward(B, xc)
+        else:
+            ctx.save_for_backward(B)
         ctx.meta = (x.dtype, x.shape, O, I, F)
         return Ut
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, dUt):
         ext = _load_ext()
-        (B,) = ctx.saved_tensors
+        B = ctx.saved_tensors[0]
         dtype, (E, C, I_), O, I, F = ctx.meta
-        dX = torch.empty(E, C, I, dtype=dtype, device=B.device)
-        ext.ubuild_bwd_dx(B, dUt.contiguous().float(), dX, O, I, F)
-        return dX, None, None, None, None
+        dU = dUt.contiguous().float()
+        dX = dB = None
+        if ctx.needs_input_grad[0]:
+            dX = torch.empty(E, C, I, dtype=dtype, device=B.device)
+            ext.ubuild_bwd_dx(B, dU, dX, O, I, F)
+        if ctx.needs_input_grad[1]:
+            dB = torch.empty(E, O, I, F, dtype=torch.float32, device=B.device)
+            ext.ubuild_bwd_db(ctx.saved_tensors[1], dU, dB, O, I, F)
+        return dX, dB, None, None, None
 
 
 def ubuild_ok(B, C, O, I, F) -> bool:
     ext = _load_ext()
-    return (ext is not None and hasattr(ext, 'ubuild_fwd')
-            and B.dtype == torch.float32 and not B.requires_grad
+    if ext is None or not hasattr(ext, 'ubuild_fwd'):
+        return False
+    if B.requires_grad and torch.is_grad_enabled():
+        if not hasattr(ext, 'ubuild_bwd_db'):
+            raise RuntimeError(
+                'se3_transformer_amd._C lacks ubuild_bwd_db; rebuild the '
+                'extension (python scripts/build_ext.py)')
+    return (B.dtype == torch.float32
             and C % 32 == 0 and O * I * F <= 343)
 
 
