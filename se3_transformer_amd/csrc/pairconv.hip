@@ -460,6 +460,18 @@ void attn2_bwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
 void norm_se3_fwd(torch::Tensor t, torch::Tensor scale, torch::Tensor out, double eps);
 void norm_se3_bwd(torch::Tensor t, torch::Tensor scale, torch::Tensor dout,
                   torch::Tensor dt, torch::Tensor dscale, double eps);
+void norm_se3_nl_fwd(torch::Tensor t, torch::Tensor scale, torch::Tensor out,
+                     double eps, int64_t nonlin);
+void norm_se3_nl_bwd(torch::Tensor t, torch::Tensor scale, torch::Tensor dout,
+                     torch::Tensor dt, torch::Tensor dscale, double eps,
+                     int64_t nonlin);
+int64_t norm_se3_gated_max_c();
+void norm_se3_gated_fwd(torch::Tensor t, torch::Tensor W, torch::Tensor out,
+                        torch::Tensor gate, double eps, int64_t nonlin);
+void norm_se3_gated_bwd(torch::Tensor t, torch::Tensor Wt, torch::Tensor gate,
+                        torch::Tensor dout, torch::Tensor dt,
+                        torch::Tensor dgate, torch::Tensor nu, double eps,
+                        int64_t nonlin);
 void pairconv_bwd_dh(torch::Tensor G, torch::Tensor Ut, torch::Tensor Wt,
                      torch::Tensor dH, int64_t mo_);
 void pairconv_bwd_dw(torch::Tensor G, torch::Tensor Ut, torch::Tensor Ht,
@@ -509,6 +521,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("attn2_bwd", &attn2_bwd, "fused neighbor attention backward");
     m.def("norm_se3_fwd", &norm_se3_fwd, "fused NormSE3 forward");
     m.def("norm_se3_bwd", &norm_se3_bwd, "fused NormSE3 backward");
+    m.def("norm_se3_nl_fwd", &norm_se3_nl_fwd,
+          "fused NormSE3 forward, nonlin 0 = GELU, 1 = identity");
+    m.def("norm_se3_nl_bwd", &norm_se3_nl_bwd,
+          "fused NormSE3 backward, nonlin 0 = GELU, 1 = identity");
+    m.def("norm_se3_gated_max_c", &norm_se3_gated_max_c,
+          "channel ceiling of the gated-scale NormSE3 kernels");
+    m.def("norm_se3_gated_fwd", &norm_se3_gated_fwd,
+          "fused gated-scale NormSE3 forward (also writes gate)");
+    m.def("norm_se3_gated_bwd", &norm_se3_gated_bwd,
+          "fused gated-scale NormSE3 backward (dt; dgate and nu for dW)");
     m.def("sh_basis_fwd", &sh_basis_fwd,
           "fused spherical-harmonics + equivariant basis (MI355X)");
     m.def("pack_w_both", &pack_w_both,

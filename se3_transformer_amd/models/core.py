@@ -76,7 +76,18 @@ class NormSE3(nn.Module):
     """Equivariant norm-gated nonlinearity: out = nonlin(scale * |x|) * x/|x|.
 
     transform.<degree>.{scale|w_gate} parameter names as the reference
-    (:123-127); only the parameter actually used is registered.
+    (:123-127); only the parameter actually used is registered. With
+    gated_scale the per-channel scale becomes a gate mixed over channels:
+    out = nonlin(|x| @ w_gate) * x/|x|.
+
+    On a GPU every variant the package builds runs the fused HIP kernels of
+    csrc/norm_se3.hip, forward and analytic backward (first order):
+    {scale, w_gate} x {exact-erf nn.GELU, nn.Identity}, for fp32/bf16
+    features of order 2d+1 in {1,3,5,7}; the gated kernels up to
+    fused.NORM_GATED_MAX_C channels. Their gate matvec stays fp32 even under
+    autocast. Anything else (tanh-GELU, other nonlinearities, f64, CPU,
+    wider gated fibers, SE3_EAGER_NORM=1) takes the eager code below, which
+    is also the parity oracle and keeps double backward.
     """
 
     def __init__(self, fiber: Fiber, nonlin=nn.GELU(), gated_scale=False, eps=1e-12):
@@ -95,23 +106,47 @@ class NormSE3(nn.Module):
                 entries['w_gate'] = nn.Parameter(rand_uniform((chan, chan), -1e-3, 1e-3))
             self.transform[str(degree)] = nn.ParameterDict(entries)
 
+    def _fused_nonlin(self):
+        """Name of the kernels' nonlinearity selector, or None for eager."""
+        if os.environ.get('SE3_EAGER_NORM') == '1':
+            return None
+        if isinstance(self.nonlin, nn.Identity):
+            return 'identity'
+        if (isinstance(self.nonlin, nn.GELU)
+                and getattr(self.nonlin, 'approximate', 'none') == 'none'):
+            return 'gelu'
+        return None
+
+    @staticmethod
+    def _fused_ok(t, gated, nonlin):
+        from ..ops import fused
+        if not (nonlin is not None and t.is_cuda and t.dim() >= 2
+                and t.shape[-1] in (1, 3, 5, 7)
+                and t.dtype in (torch.float32, torch.bfloat16)
+                and fused.ext_available()):
+            return False
+        if gated and t.shape[-2] > fused.NORM_GATED_MAX_C:
+            return False    # LDS tile of the gated kernels: eager above it
+        # scale+GELU is the original kernel pair; the rest need the newer
+        # entry points, and a build without them raises
+        return (not gated and nonlin == 'gelu') or fused.norm_variants_ok()
+
     def forward(self, features):
-        from ..ops.fused import ext_available, norm_se3
-        use_fused = (not self.gated_scale and isinstance(self.nonlin, nn.GELU)
-                     and getattr(self.nonlin, 'approximate', 'none') == 'none'
-                     and os.environ.get('SE3_EAGER_NORM') != '1')
+        from ..ops import fused
+        nonlin = self._fused_nonlin()
         output = {}
         for degree, t in features.items():
-            if (use_fused and t.is_cuda and t.shape[-1] in (1, 3, 5, 7)
-                    and t.dtype in (torch.float32, torch.bfloat16)
-                    and ext_available()):
-                output[degree] = norm_se3(t.contiguous(),
-                                          self.transform[degree]['scale'],
-                                          self.eps)
+            params = self.transform[degree]
+            if self._fused_ok(t, 'w_gate' in params, nonlin):
+                if 'scale' in params:
+                    output[degree] = fused.norm_se3(
+                        t.contiguous(), params['scale'], self.eps, nonlin)
+                else:
+                    output[degree] = fused.norm_se3_gated(
+                        t.contiguous(), params['w_gate'], self.eps, nonlin)
                 continue
             norm = t.norm(dim=-1, keepdim=True).clamp(min=self.eps)
             phase = t / norm
-            params = self.transform[degree]
             if 'scale' in params:
                 scale = params['scale'].to(t.dtype)
                 transformed = norm.squeeze(-1) * scale

@@ -212,17 +212,25 @@ def fused_pairconv(H, W, bias, Ut, mo):
     return _FusedPairConv.apply(H, W, bias, Ut, mo)
 
 
+NORM_NONLIN = {'gelu': 0, 'identity': 1}   # selector of csrc/norm_se3.hip
+
+
 class _NormSE3Fn(torch.autograd.Function):
-    """Fused equivariant norm-gate (csrc/norm_se3.hip), scale path."""
+    """Fused equivariant norm-gate (csrc/norm_se3.hip), scale path.
+    nl selects the nonlinearity (NORM_NONLIN): exact-erf GELU or identity."""
 
     @staticmethod
-    def forward(ctx, t, scale, eps):
+    def forward(ctx, t, scale, eps, nl=0):
         ext = _load_ext()
         s32 = scale.detach().reshape(-1).float().contiguous()
         out = torch.empty_like(t)
-        ext.norm_se3_fwd(t, s32, out, eps)
+        if nl == 0:
+            ext.norm_se3_fwd(t, s32, out, eps)
+        else:
+            ext.norm_se3_nl_fwd(t, s32, out, eps, nl)
         ctx.save_for_backward(t, s32)
         ctx.eps = eps
+        ctx.nl = nl
         ctx.scale_shape = scale.shape
         ctx.scale_dtype = scale.dtype
         return out
@@ -233,12 +241,82 @@ class _NormSE3Fn(torch.autograd.Function):
         t, s32 = ctx.saved_tensors
         dt = torch.empty_like(t)
         dscale = torch.zeros_like(s32)
-        ext.norm_se3_bwd(t, s32, dout.contiguous(), dt, dscale, ctx.eps)
-        return dt, dscale.view(ctx.scale_shape).to(ctx.scale_dtype), None
+        if ctx.nl == 0:
+            ext.norm_se3_bwd(t, s32, dout.contiguous(), dt, dscale, ctx.eps)
+        else:
+            ext.norm_se3_nl_bwd(t, s32, dout.contiguous(), dt, dscale,
+                                ctx.eps, ctx.nl)
+        return (dt, dscale.view(ctx.scale_shape).to(ctx.scale_dtype),
+                None, None)
 
 
-def norm_se3(t, scale, eps):
-    return _NormSE3Fn.apply(t, scale, eps)
+class _NormSE3GatedFn(torch.autograd.Function):
+    """Fused gated-scale NormSE3 (csrc/norm_se3.hip):
+    out = g(|t| @ w_gate) * t/|t| with w_gate (C, C) and the norms kept in
+    fp32 in front of the nonlinearity. The forward saves gate (N, C) fp32;
+    the backward kernel returns dt plus dgate and nu, and
+    dW = nu^T @ dgate is one library GEMM (deterministic, no atomics).
+    First order only."""
+
+    @staticmethod
+    def forward(ctx, t, w_gate, eps, nl=0):
+        ext = _load_ext()
+        w32 = w_gate.detach().float().contiguous()
+        out = torch.empty_like(t)
+        gate = torch.empty(t.shape[:-1], dtype=torch.float32, device=t.device)
+        ext.norm_se3_gated_fwd(t, w32, out, gate, eps, nl)
+        ctx.save_for_backward(t, w32, gate)
+        ctx.eps = eps
+        ctx.nl = nl
+        ctx.w_dtype = w_gate.dtype
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        ext = _load_ext()
+        t, w32, gate = ctx.saved_tensors
+        C = w32.shape[0]
+        dt = torch.empty_like(t)
+        dgate = torch.empty_like(gate)
+        nu = torch.empty_like(gate)
+        ext.norm_se3_gated_bwd(t, w32.t().contiguous(), gate,
+                               dout.contiguous(), dt, dgate, nu,
+                               ctx.eps, ctx.nl)
+        dW = None
+        if ctx.needs_input_grad[1]:
+            dW = torch.mm(nu.view(-1, C).t(), dgate.view(-1, C)) \
+                .to(ctx.w_dtype)
+        return dt, dW, None, None
+
+
+def norm_variants_ok() -> bool:
+    """True when the extension carries the identity and gated-scale NormSE3
+    kernels; a stale build is an error, not a reason to run eager."""
+    ext = _load_ext()
+    if ext is None:
+        return False
+    if not (hasattr(ext, 'norm_se3_nl_fwd') and hasattr(ext, 'norm_se3_nl_bwd')
+            and hasattr(ext, 'norm_se3_gated_fwd')
+            and hasattr(ext, 'norm_se3_gated_bwd')):
+        raise RuntimeError(
+            'se3_transformer_amd._C lacks the norm_se3_nl_*/norm_se3_gated_* '
+            'entry points; rebuild the extension '
+            '(python scripts/build_ext.py)')
+    return True
+
+
+# Channel ceiling of the gated kernels (GATED_MAX_C in csrc/norm_se3.hip):
+# their LDS tile is 16*C bytes per block.
+NORM_GATED_MAX_C = 2048
+
+
+def norm_se3(t, scale, eps, nonlin='gelu'):
+    return _NormSE3Fn.apply(t, scale, eps, NORM_NONLIN[nonlin])
+
+
+def norm_se3_gated(t, w_gate, eps, nonlin='gelu'):
+    return _NormSE3GatedFn.apply(t, w_gate, eps, NORM_NONLIN[nonlin])
 
 
 class _AttnFn(torch.autograd.Function):
