@@ -361,16 +361,6 @@ void norm_se3_nl_bwd(torch::Tensor t, torch::Tensor scale, torch::Tensor dout,
     TORCH_CHECK(err == hipSuccess, "norm_se3_bwd: ", hipGetErrorString(err));
 }
 
-void norm_se3_fwd(torch::Tensor t, torch::Tensor scale, torch::Tensor out,
-                  double eps) {
-    norm_se3_nl_fwd(t, scale, out, eps, 0);
-}
-
-void norm_se3_bwd(torch::Tensor t, torch::Tensor scale, torch::Tensor dout,
-                  torch::Tensor dt, torch::Tensor dscale, double eps) {
-    norm_se3_nl_bwd(t, scale, dout, dt, dscale, eps, 0);
-}
-
 int64_t norm_se3_gated_max_c() { return GATED_MAX_C; }
 
 static void check_f32_nc(const torch::Tensor& x, long N, int C, const char* name) {

@@ -15,58 +15,42 @@
 //
 // Layouts:
 //   H   (E, 128)      bf16   radial trunk activations (k-contiguous)
-//   W   (mo*miF, 128) bf16   net.6 weight, torch Linear layout (out,in)
+//   P   (mo*miF*128)  bf16   net.6 weight packed in MFMA A-fragment order
+//                            [mo/8][miF/32][wm4][mf4][kit4][lane64][8]
 //   Ut  (miF, O, E)   bf16   basis-contracted features, e-contiguous
 //   out (E, mo, O)    f32    pre-initialized with the bias term; kernel adds
 //
-// Tile: block = 512 threads (8 waves) owns (64 edges) x (8 mo); loops over
-// miF in chunks of 32; per chunk an MFMA GEMM of (256 n-rows x 64 e-cols, K=128)
-// with n = 8mo x 32urow, then a VALU contraction against u_lds into
-// per-lane register accumulators (the cross-lane l4 reduce is deferred to
-// after the chunk loop). Each (e, mo) output is owned by exactly one block:
+// Tile: block = 512 threads (8 waves) owns (64 edges) x (8*MB2 mo). The H
+// tile is staged to LDS once. The block then loops over miF in chunks of 32:
+// the chunk's u tile goes global -> LDS directly (the co-resident block
+// covers its latency; a register pipeline for it measured slower), and for
+// each of the MB2 mo-sub-blocks in turn an MFMA GEMM of (256 n-rows x 64
+// e-cols, K=128), n = 8mo x 32urow, is followed by a VALU contraction
+// against u_lds into per-lane accumulators, a cross-lane reduce and an add
+// into the LDS partial. Each (e, mo) output is owned by exactly one block:
 // no atomics anywhere.
-//
-// Software pipeline (round 2): the next chunk's u tile is loaded into
-// registers while the current chunk's MFMA + epilogue run, so the
-// u-stage's HBM/L2 latency hides under compute instead of serializing
-// each chunk (the round-1 PMC analysis measured ~3.5k-cycle wave stalls
-// per chunk from the serialized u-stage -> W-frags round trips).
 
-#include <torch/extension.h>
 #include <hip/hip_runtime.h>
-#include <ATen/hip/HIPContext.h>
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
+#include "pairconv_common.h"
 
 #define BLK_E 64
 #define BLK_MO 8
 #define UCHUNK 32
-#define KDIM 128
-#define NTHREADS 512
-
-__device__ __forceinline__ float bf16_to_f32(unsigned short u) {
-    union { unsigned int i; float f; } v;
-    v.i = ((unsigned int)u) << 16;
-    return v.f;
-}
 
 // MB2 = mo-blocks (of 8) processed per workgroup against ONE staged u chunk.
 // MB2=2 halves the u-chunk HBM traffic (u is re-read per mo-block otherwise)
 // while keeping 2-blocks/CU residency: the two sub-blocks run serially, so
 // the MFMA accumulator registers are reused, only the LDS `part` doubles
-// (O=7: 16K h + 28K u + 28K part = 72 KiB <= 80 KiB per block).
+// (O=7: 16K h + 32K u + 28K part = 76 KiB <= 80 KiB per block).
 // WP = W-fragment software pipeline: the next sub-block's 16 A-fragments
 // are prefetched into registers during the current sub-block's epilogue
 // (where the MFMA accumulators are dead), so each MFMA phase starts with
 // its operands already in flight instead of paying a fresh L2/HBM round
-// trip (T14 applied to the W stream).
-// ES = epilogue split: process the padded o range in two passes with half
-// the persistent accumulators (frees VGPRs for the WP prefetch at O>=5)
-template <int O, int UU, int MB2, int WP, int ES>   // UU = 16B u-units register-staged per thread
-__global__ void __launch_bounds__(NTHREADS, 4)   // cap VGPR<=128: 2 blocks/CU
+// trip.
+template <int O, int MB2, int WP>
+__global__ void __launch_bounds__(NT, 4)   // cap VGPR<=128: 2 blocks/CU
 pairconv_fwd_kernel(const __bf16* __restrict__ H,
-                    const __bf16* __restrict__ P,   // packed W: [mo/8][miF/32][wm4][mf4][kit4][lane64][8]
+                    const __bf16* __restrict__ P,
                     const __bf16* __restrict__ Ut,
                     float* __restrict__ out,
                     int E, int mo, int miF, int nmemb, int coh) {
@@ -88,112 +72,41 @@ pairconv_fwd_kernel(const __bf16* __restrict__ H,
     const int l15 = lane & 15;
     const int l4 = lane >> 4;          // 0..3
 
-    // cohort mapping: all concurrently-resident blocks on one XCD share the
-    // same mo-block (=> the same packed-W slice stays in that XCD's L2).
-    int eb, mb;
-    if (coh) {
-        int x = blockIdx.x & 7, r = blockIdx.x >> 3;
-        eb = r % nmemb;
-        mb = x + 8 * (r / nmemb);
-    } else {
-        eb = blockIdx.x % nmemb;
-        mb = blockIdx.x / nmemb;
-    }
+    int eb, mb;                        // the cohort shares an mo-block group
+    cohort_map(coh, nmemb, eb, mb);
     const int e0 = eb * BLK_E;
     const int mo0 = mb * BLK_MO * MB2;
 
-    // ---- stage H tile (64 x 128 bf16), XOR-swizzled 16B slots within each row
-    {
-        for (int i = tid; i < (BLK_E * KDIM) / 8; i += NTHREADS) {  // 16B units
-            int e = i >> 4;             // 16 units per row
-            int k16 = i & 15;           // 16B slot
-            int dst = e * 256 + ((k16 * 16) ^ ((e & 15) << 4));
-            bf16x8 v;
-            if (e0 + e < E) {
-                v = *reinterpret_cast<const bf16x8*>(H + (size_t)(e0 + e) * KDIM + k16 * 8);
-            } else {
-                v = bf16x8(0);
-            }
-            *reinterpret_cast<bf16x8*>(reinterpret_cast<char*>(h_lds) + dst) = v;
-        }
-        // zero partial accumulator + the u pad lanes (o in [O, 8) are never
-        // overwritten by staging, so one upfront clear keeps them zero)
-        for (int i = tid; i < BLK_E * BLK_MO * MB2 * O; i += NTHREADS) part[i] = 0.f;
-        for (int i = tid; i < UCHUNK * BLK_E * 8 / 8; i += NTHREADS)
-            *reinterpret_cast<bf16x8*>(u_lds + (size_t)i * 8) = bf16x8(0);
-    }
+    stage_h_tile(h_lds, H, e0, E, tid);
+    // zero partial accumulator + the u pad lanes (o in [O, 8) are never
+    // overwritten by staging, so one upfront clear keeps them zero)
+    for (int i = tid; i < BLK_E * BLK_MO * MB2 * O; i += NT) part[i] = 0.f;
+    for (int i = tid; i < UCHUNK * BLK_E * 8 / 8; i += NT)
+        *reinterpret_cast<bf16x8*>(u_lds + (size_t)i * 8) = bf16x8(0);
 
     constexpr int UTOT = (UCHUNK * O * BLK_E) / 8;   // u chunk in 16B units
-    bf16x8 u_reg[UU > 0 ? UU : 1];
-    auto load_u = [&](int c) {
-        const int uc0 = c * UCHUNK;
-#pragma unroll
-        for (int t = 0; t < UU; ++t) {
-            int i = tid + t * NTHREADS;
-            if (i < UTOT) {
-                int ro = i >> 3;            // (urow*O + o)
-                int eu = (i & 7) * 8;       // e offset within 64
-                const __bf16* src = Ut + ((size_t)(uc0 + (ro / O)) * O + (ro % O)) * E + e0 + eu;
-                if (e0 + eu + 8 <= E) {
-                    u_reg[t] = *reinterpret_cast<const bf16x8*>(src);
-                } else {
-                    bf16x8 v(0);
-                    for (int j = 0; j < 8; ++j)
-                        if (e0 + eu + j < E) v[j] = src[j];
-                    u_reg[t] = v;
-                }
-            }
-        }
-    };
-
-    load_u(0);
-
     const int nchunks = miF / UCHUNK;
-    // W-pipeline state: the 16 A-fragments of the NEXT (chunk, sub) pair
     auto pb_of = [&](int cc, int ss) {
         return P + ((((size_t)(mb * MB2 + ss) * (miF / 32) + cc) * 4 + wm) * 4) * 4 * 64 * 8
                + (size_t)lane * 8;
     };
+    // W-pipeline state: the 16 A-fragments of the NEXT (chunk, sub) pair
     bf16x8 a_pre[WP ? 16 : 1];
     if (WP) {
 #pragma unroll
-        for (int f = 0; f < 16; ++f)
-            a_pre[f] = *reinterpret_cast<const bf16x8*>(pb_of(0, 0) + (size_t)f * 512);
+        for (int f = 0; f < 16; ++f) a_pre[f] = load_wfrag(pb_of(0, 0), f);
     }
     __syncthreads();
 
     for (int c = 0; c < nchunks; ++c) {
-        // ---- commit the staged u chunk, scattered to [urow][e][o(pad 8)]
-#pragma unroll
-        for (int t = 0; t < UU; ++t) {
-            int i = tid + t * NTHREADS;
-            if (i < UTOT) {
-                int ro = i >> 3, eu = (i & 7) * 8;
-                const int ur = ro / O, o = ro % O;
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    u_lds[((size_t)ur * BLK_E + eu + j) * 8 + o] = u_reg[t][j];
-            }
-        }
-        // tail units beyond the register budget: direct load (UU*NT >= UTOT
-        // for the shipped instantiations — loop compiles away)
-        for (int i = tid + UU * NTHREADS; i < UTOT; i += NTHREADS) {
-            int ro = i >> 3, eu = (i & 7) * 8;
-            const __bf16* src = Ut + ((size_t)(c * UCHUNK + (ro / O)) * O + (ro % O)) * E + e0 + eu;
-            bf16x8 v;
-            if (e0 + eu + 8 <= E) {
-                v = *reinterpret_cast<const bf16x8*>(src);
-            } else {
-                v = bf16x8(0);
-                for (int j = 0; j < 8; ++j)
-                    if (e0 + eu + j < E) v[j] = src[j];
-            }
+        // ---- stage the u chunk, scattered to [urow][e][o(pad 8)]
+        for (int i = tid; i < UTOT; i += NT) {
+            int ro = i >> 3;            // (urow*O + o)
+            int eu = (i & 7) * 8;       // e offset within 64
             const int ur = ro / O, o = ro % O;
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                u_lds[((size_t)ur * BLK_E + eu + j) * 8 + o] = v[j];
+            bf16x8 v = load_edges8(Ut + ((size_t)(c * UCHUNK + ur) * O + o) * E, e0 + eu, E);
+            commit_opad(u_lds, ur, eu, o, v);
         }
-        if (c + 1 < nchunks) load_u(c + 1);   // issue next chunk's loads early
         __syncthreads();
 
         // ---- per mo-sub-block: GEMM + epilogue against the SAME u chunk.
@@ -205,34 +118,10 @@ pairconv_fwd_kernel(const __bf16* __restrict__ H,
         if (MB2 > 1 && sub > 0) __builtin_amdgcn_sched_barrier(0);
         // ---- GEMM: R^T tile (256 n x 64 e), K=128
         f32x4 acc[4][2];
-#pragma unroll
-        for (int mf = 0; mf < 4; ++mf)
-#pragma unroll
-            for (int ef = 0; ef < 2; ++ef) acc[mf][ef] = f32x4(0.f);
-
         const __bf16* pbase = pb_of(c, sub);
-#pragma unroll
-        for (int kit = 0; kit < 4; ++kit) {
-            const int k0 = kit * 32 + l4 * 8;
-            bf16x8 a[4], b[2];
-#pragma unroll
-            for (int mf = 0; mf < 4; ++mf) {
-                a[mf] = WP ? a_pre[mf * 4 + kit]
-                           : *reinterpret_cast<const bf16x8*>(
-                                 pbase + ((size_t)mf * 4 + kit) * 64 * 8);
-            }
-#pragma unroll
-            for (int ef = 0; ef < 2; ++ef) {
-                int e = we * 32 + ef * 16 + l15;
-                int byte = e * 256 + ((k0 * 2) ^ ((e & 15) << 4));
-                b[ef] = *reinterpret_cast<const bf16x8*>(reinterpret_cast<char*>(h_lds) + byte);
-            }
-#pragma unroll
-            for (int mf = 0; mf < 4; ++mf)
-#pragma unroll
-                for (int ef = 0; ef < 2; ++ef)
-                    acc[mf][ef] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[mf], b[ef], acc[mf][ef], 0, 0, 0);
-        }
+        mfma_rtile(acc, h_lds, we, l15, l4, [&](int mf, int kit) {
+            return WP ? a_pre[mf * 4 + kit] : load_wfrag(pbase, mf * 4 + kit);
+        });
         if (WP) {
             // prefetch the NEXT sub-block/chunk's fragments now — their
             // L2/HBM latency hides under the epilogue below (acc is the
@@ -242,30 +131,19 @@ pairconv_fwd_kernel(const __bf16* __restrict__ H,
             if (nc2 == nchunks) { ns = sub; nc2 = c; }   // tail: benign refetch
             const __bf16* pn = pb_of(nc2, ns);
 #pragma unroll
-            for (int f = 0; f < 16; ++f)
-                a_pre[f] = *reinterpret_cast<const bf16x8*>(pn + (size_t)f * 512);
+            for (int f = 0; f < 16; ++f) a_pre[f] = load_wfrag(pn, f);
         }
 
-        // ---- epilogue: contract acc against u_lds into s[ef][moi][o-pairs].
+        // ---- epilogue: contract acc against u_lds into s[ef][moi][o-pair].
         // One ds_read_b128 per (row, e) covers all 8 padded o; the o-pair
-        // float2 accumulation maps onto v_pk_fma_f32. With ES (epilogue
-        // split), the o range is processed in NH sequential halves with
-        // only PH o-pairs of accumulators live (re-reads u but halves the
-        // persistent s footprint — funds WP at the big orders); a
-        // sched_barrier keeps the halves from being re-merged.
-        typedef __attribute__((ext_vector_type(2))) float f32x2e;
-        constexpr int PH = ES ? 2 : 4;   // o-pairs held per pass
-        constexpr int NH = 4 / PH;
-#pragma unroll
-        for (int oh = 0; oh < NH; ++oh) {
-        if (NH > 1 && oh > 0) __builtin_amdgcn_sched_barrier(0);
-        f32x2e s[2][2][PH];
+        // float2 accumulation maps onto v_pk_fma_f32.
+        f32x2 s[2][2][4];
 #pragma unroll
         for (int ef = 0; ef < 2; ++ef)
 #pragma unroll
             for (int mi_ = 0; mi_ < 2; ++mi_)
 #pragma unroll
-                for (int p_ = 0; p_ < PH; ++p_) s[ef][mi_][p_] = f32x2e{0.f, 0.f};
+                for (int p_ = 0; p_ < 4; ++p_) s[ef][mi_][p_] = f32x2{0.f, 0.f};
 
 #pragma unroll
         for (int mf = 0; mf < 2; ++mf) {   // mf and mf+2 share urow (rows r, r+32)
@@ -281,9 +159,8 @@ pairconv_fwd_kernel(const __bf16* __restrict__ H,
                     bf16x8 uv8 = *reinterpret_cast<const bf16x8*>(
                         u_lds + ((size_t)urow * BLK_E + e) * 8);
 #pragma unroll
-                    for (int p_ = 0; p_ < PH; ++p_) {
-                        const int pp = oh * PH + p_;
-                        f32x2e u2 = {(float)uv8[2 * pp], (float)uv8[2 * pp + 1]};
+                    for (int p_ = 0; p_ < 4; ++p_) {
+                        f32x2 u2 = {(float)uv8[2 * p_], (float)uv8[2 * p_ + 1]};
                         s[ef][0][p_] += rv0 * u2;
                         s[ef][1][p_] += rv1 * u2;
                     }
@@ -297,10 +174,10 @@ pairconv_fwd_kernel(const __bf16* __restrict__ H,
 #pragma unroll
             for (int mi_ = 0; mi_ < 2; ++mi_)
 #pragma unroll
-                for (int p_ = 0; p_ < PH; ++p_) {
+                for (int p_ = 0; p_ < 4; ++p_) {
 #pragma unroll
                     for (int c2 = 0; c2 < 2; ++c2) {
-                        if (2 * (oh * PH + p_) + c2 >= O) break;
+                        if (2 * p_ + c2 >= O) break;
                         float v = s[ef][mi_][p_][c2];
                         v += __shfl_xor(v, 16);
                         v += __shfl_xor(v, 32);
@@ -315,21 +192,19 @@ pairconv_fwd_kernel(const __bf16* __restrict__ H,
                 for (int mi_ = 0; mi_ < 2; ++mi_) {
                     const int moi = sub * BLK_MO + wm * 2 + mi_;
 #pragma unroll
-                    for (int o = 2 * oh * PH;
-                         o < 2 * (oh + 1) * PH && o < O; ++o) {
+                    for (int o = 0; o < O; ++o) {
                         float* p = part + ((size_t)e * (BLK_MO * MB2) + moi) * O + o;
-                        *p += s[ef][mi_][(o >> 1) - oh * PH][o & 1];
+                        *p += s[ef][mi_][o >> 1][o & 1];
                     }
                 }
             }
         }
-        }   // oh
         }   // sub
         __syncthreads();
     }
 
     // ---- write out: out[e0+e][mo0+moi][o] += partial
-    for (int i = tid; i < BLK_E * BLK_MO * MB2 * O; i += NTHREADS) {
+    for (int i = tid; i < BLK_E * BLK_MO * MB2 * O; i += NT) {
         int o = i % O;
         int moi = (i / O) % (BLK_MO * MB2);
         int e = i / (O * BLK_MO * MB2);
@@ -340,76 +215,29 @@ pairconv_fwd_kernel(const __bf16* __restrict__ H,
     }
 }
 
-template <int O>
-static void launch_fwd(const torch::Tensor& H, const torch::Tensor& W,
+// One kernel per (O, MB2); both choices are functions of the shape alone
+// (measurements in profiles/LADDER.md):
+//   MB2 = 2 wherever mo allows it — sharing a staged u chunk between two
+//         mo-blocks halves the u traffic.
+//   WP on at O=3,5 (+7% at O=5); at O=7 the held prefetch registers spill
+//         the epilogue (108 B/lane, -9%); O=1 has only been run without it.
+template <int O, int MB2>
+static void launch_fwd(const torch::Tensor& H, const torch::Tensor& P,
                        const torch::Tensor& Ut, torch::Tensor& out,
                        int E, int mo, int miF) {
+    constexpr int WP = (O == 3 || O == 5) ? 1 : 0;
     int nmemb = (E + BLK_E - 1) / BLK_E;
-    auto stream = at::cuda::getCurrentHIPStream();
-    // UU: 16B u-units register-staged per thread for the next-chunk pipeline.
-    // MEASURED NEGATIVE on MI355X for the hot O=7 shape (UU=0: 239.6 TF/s,
-    // UU=1: 217, UU=2: 221, UU=4: 153 — the VGPR spill the staging forces
-    // under the 2-blocks/CU cap costs more than the hidden u latency, and
-    // the co-resident block already covers most of the stall). Default 0;
-    // SE3_FWD_UU kept for A/B runs.
-    const char* uu_env = getenv("SE3_FWD_UU");
-    int uu_sel = uu_env ? atoi(uu_env) : 0;
-    constexpr int UUfull = (UCHUNK * O * BLK_E / 8 + NTHREADS - 1) / NTHREADS;
-    int uu = uu_sel < 0 ? 0 : uu_sel;
-    if (uu > 2) uu = 2;
-    if (uu > UUfull) uu = UUfull;
-    // MB2: mo-blocks per workgroup sharing one staged u chunk (halves u
-    // traffic). Default 2 where mo allows; SE3_FWD_MB2=1 forces the old
-    // one-block grid for A/B runs.
-    const char* mb_env = getenv("SE3_FWD_MB2");
-    int mb2 = (mb_env ? atoi(mb_env) : 2);
-    if (mb2 != 1 && mo % (BLK_MO * 2) != 0) mb2 = 1;
-    if (mb2 != 1) mb2 = 2;
-    // WP: W-fragment software pipeline (prefetch next sub-block's A-frags
-    // under the epilogue). Only instantiated with UU=0. Measured on MI355X:
-    // +7% at O=5 (347.9 -> 372 TF/s at the (2,2) shape), -9% at O=7 (the
-    // held prefetch registers push the epilogue to ~108 B/lane spill), so
-    // the default is per-O; SE3_FWD_WP overrides for A/B runs.
-    const char* wp_env = getenv("SE3_FWD_WP");
-    int wp = wp_env ? atoi(wp_env) : ((O == 3 || O == 5) ? 1 : 0);
-    if (wp) uu = 0;
-    // ES (epilogue split) — A/B knob for the large orders; see the kernel
-    const char* es_env = getenv("SE3_FWD_ES");
-    int es = es_env ? atoi(es_env) : 0;
-    if (O < 5) es = 0;
-    if (es) uu = 0;
-    int ng = mo / (BLK_MO * mb2);
+    int ng = mo / (BLK_MO * MB2);
     int coh = (ng % 8 == 0) ? 1 : 0;
-    dim3 grid(nmemb * ng);
     size_t lds = 16384 + (size_t)UCHUNK * BLK_E * 8 * 2
-                 + (size_t)BLK_E * BLK_MO * mb2 * O * 4;
-#define LAUNCH_FWD(UU, MB2, WPv, ESv)                                                        \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(pairconv_fwd_kernel<O, UU, MB2, WPv, ESv>), grid,     \
-                       dim3(NTHREADS), lds, stream,                                          \
-                       reinterpret_cast<const __bf16*>(H.data_ptr()),                        \
-                       reinterpret_cast<const __bf16*>(W.data_ptr()),                        \
-                       reinterpret_cast<const __bf16*>(Ut.data_ptr()),                       \
-                       out.data_ptr<float>(), E, mo, miF, nmemb, coh)  /* W arg = packed P */
-    if (mb2 == 2) {
-        if (es && wp) { LAUNCH_FWD(0, 2, 1, 1); }
-        else if (es) { LAUNCH_FWD(0, 2, 0, 1); }
-        else if (wp) { LAUNCH_FWD(0, 2, 1, 0); }
-        else switch (uu) {
-            case 0: LAUNCH_FWD(0, 2, 0, 0); break;
-            case 1: LAUNCH_FWD(1, 2, 0, 0); break;
-            default: LAUNCH_FWD(2, 2, 0, 0); break;
-        }
-    } else {
-        if (es && wp) { LAUNCH_FWD(0, 1, 1, 1); }
-        else if (es) { LAUNCH_FWD(0, 1, 0, 1); }
-        else if (wp) { LAUNCH_FWD(0, 1, 1, 0); }
-        else switch (uu) {
-            case 0: LAUNCH_FWD(0, 1, 0, 0); break;
-            case 1: LAUNCH_FWD(1, 1, 0, 0); break;
-            default: LAUNCH_FWD(2, 1, 0, 0); break;
-        }
-    }
-#undef LAUNCH_FWD
+                 + (size_t)BLK_E * BLK_MO * MB2 * O * 4;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(pairconv_fwd_kernel<O, MB2, WP>),
+                       dim3(nmemb * ng), dim3(NT), lds,
+                       at::cuda::getCurrentHIPStream(),
+                       reinterpret_cast<const __bf16*>(H.data_ptr()),
+                       reinterpret_cast<const __bf16*>(P.data_ptr()),
+                       reinterpret_cast<const __bf16*>(Ut.data_ptr()),
+                       out.data_ptr<float>(), E, mo, miF, nmemb, coh);
 }
 
 void pairconv_fwd(torch::Tensor H, torch::Tensor W, torch::Tensor Ut,
@@ -429,13 +257,10 @@ void pairconv_fwd(torch::Tensor H, torch::Tensor W, torch::Tensor Ut,
     TORCH_CHECK(out.size(0) == E && out.size(1) == mo && out.size(2) == O);
     TORCH_CHECK(miF % UCHUNK == 0, "miF must be a multiple of 32");
     TORCH_CHECK(mo % BLK_MO == 0, "mo must be a multiple of 8");
-    switch (O) {
-        case 1: launch_fwd<1>(H, W, Ut, out, E, mo, miF); break;
-        case 3: launch_fwd<3>(H, W, Ut, out, E, mo, miF); break;
-        case 5: launch_fwd<5>(H, W, Ut, out, E, mo, miF); break;
-        case 7: launch_fwd<7>(H, W, Ut, out, E, mo, miF); break;
-        default: TORCH_CHECK(false, "unsupported output order ", O);
-    }
+    DISPATCH_O(O, {
+        if (mo % (BLK_MO * 2) == 0) launch_fwd<kO, 2>(H, W, Ut, out, E, mo, miF);
+        else launch_fwd<kO, 1>(H, W, Ut, out, E, mo, miF);
+    });
     hipError_t err = hipGetLastError();
     TORCH_CHECK(err == hipSuccess, "pairconv_fwd launch failed: ", hipGetErrorString(err));
 }
@@ -457,9 +282,6 @@ void attn2_bwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                torch::Tensor dq, torch::Tensor dk, torch::Tensor dv,
                int64_t n, int64_t heads, double scale, bool kv_one,
                int64_t jr, int64_t rot);
-void norm_se3_fwd(torch::Tensor t, torch::Tensor scale, torch::Tensor out, double eps);
-void norm_se3_bwd(torch::Tensor t, torch::Tensor scale, torch::Tensor dout,
-                  torch::Tensor dt, torch::Tensor dscale, double eps);
 void norm_se3_nl_fwd(torch::Tensor t, torch::Tensor scale, torch::Tensor out,
                      double eps, int64_t nonlin);
 void norm_se3_nl_bwd(torch::Tensor t, torch::Tensor scale, torch::Tensor dout,
@@ -519,8 +341,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("attn2_fwd", &attn2_fwd,
           "fused neighbor attention fwd (online softmax, in-kernel rotary)");
     m.def("attn2_bwd", &attn2_bwd, "fused neighbor attention backward");
-    m.def("norm_se3_fwd", &norm_se3_fwd, "fused NormSE3 forward");
-    m.def("norm_se3_bwd", &norm_se3_bwd, "fused NormSE3 backward");
     m.def("norm_se3_nl_fwd", &norm_se3_nl_fwd,
           "fused NormSE3 forward, nonlin 0 = GELU, 1 = identity");
     m.def("norm_se3_nl_bwd", &norm_se3_nl_bwd,

@@ -12,24 +12,8 @@
 //
 // dR / R are never written to global memory anywhere.
 
-#include <torch/extension.h>
 #include <hip/hip_runtime.h>
-#include <ATen/hip/HIPContext.h>
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-#define KDIM 128
-#define NT 512
-
-__device__ __forceinline__ float b2f(__bf16 x) { return (float)x; }
-
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-
-__device__ __forceinline__ f32x2 b2f2(bf16x2 v) {
-    return f32x2{(float)v[0], (float)v[1]};
-}
+#include "pairconv_common.h"
 
 // ---------------------------------------------------------------------------
 // B1: dH[e,k] = sum_n dR[e,n] W[n,k]
@@ -43,7 +27,7 @@ pairconv_bwd_dh_kernel(const __bf16* __restrict__ Gt,  // (mo, O, E) bf16
                        const __bf16* __restrict__ Ut,  // (miF, O, E) bf16
                        const __bf16* __restrict__ P1,  // packed W: [mo/8][miF/32][wk2][kf4][ns8][lane64][8]
                        float* __restrict__ dH,         // (E, 128) f32 (zeroed)
-                       int E, int mo, int miF, int nsplit, int nmemb, int coh) {
+                       int E, int mo, int miF, int nsplit, int nmemb) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // u/g tiles are [row][e][o PADDED to 8]: the dR build then reads ONE
     // 16B vector per (row, e) and contracts with v_dot2_f32_bf16 — no
@@ -59,7 +43,10 @@ pairconv_bwd_dh_kernel(const __bf16* __restrict__ Gt,  // (mo, O, E) bf16
     const int l4 = lane >> 4;
     const int we = wid >> 1;          // 0..3: e-group of 16
     const int wk = wid & 1;           // 0..1: k-group of 64
-    // L3-panel mapping (see pairconv.hip): PS split-slices x PE e-blocks
+    // panel mapping: the grid is cut into panels of PS split-slices x PE
+    // e-blocks, numbered e-block fastest, so the blocks in flight together
+    // re-read the packed-W of few split-slices and the u/g tiles of few
+    // edge blocks. The launcher rounds the grid up to whole panels.
     const int PS = 4, PE = 128;
     int panels_x = (nmemb + PE - 1) / PE;
     int within = blockIdx.x % (PS * PE);
@@ -86,13 +73,8 @@ pairconv_bwd_dh_kernel(const __bf16* __restrict__ Gt,  // (mo, O, E) bf16
     auto load_g = [&](int mb) {
         if (tid < GTOT) {
             int ro = tid >> 3, eu = (tid & 7) * 8;   // ro = m*O+o
-            const __bf16* src = Gt + ((size_t)(mb * 8 + ro / O) * O + (ro % O)) * E + e0 + eu;
-            if (e0 + eu + 8 <= E) g_reg = *reinterpret_cast<const bf16x8*>(src);
-            else {
-                bf16x8 v(0);
-                for (int j = 0; j < 8; ++j) if (e0 + eu + j < E) v[j] = src[j];
-                g_reg = v;
-            }
+            g_reg = load_edges8(Gt + ((size_t)(mb * 8 + ro / O) * O + (ro % O)) * E,
+                                e0 + eu, E);
         }
     };
     auto load_u = [&](int cb) {
@@ -101,13 +83,8 @@ pairconv_bwd_dh_kernel(const __bf16* __restrict__ Gt,  // (mo, O, E) bf16
             int i = tid + t * NT;
             if (i < UTOTd) {
                 int ro = i >> 3, eu = (i & 7) * 8;
-                const __bf16* src = Ut + ((size_t)(cb * 32 + ro / O) * O + (ro % O)) * E + e0 + eu;
-                if (e0 + eu + 8 <= E) u_reg[t] = *reinterpret_cast<const bf16x8*>(src);
-                else {
-                    bf16x8 v(0);
-                    for (int j = 0; j < 8; ++j) if (e0 + eu + j < E) v[j] = src[j];
-                    u_reg[t] = v;
-                }
+                u_reg[t] = load_edges8(Ut + ((size_t)(cb * 32 + ro / O) * O + (ro % O)) * E,
+                                       e0 + eu, E);
             }
         }
     };
@@ -125,32 +102,21 @@ pairconv_bwd_dh_kernel(const __bf16* __restrict__ Gt,  // (mo, O, E) bf16
             int i = tid + t * NT;
             if (i < UTOTd) {
                 int ro = i >> 3, eu = (i & 7) * 8;
-                const int ur = ro / O, o = ro % O;
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    u_lds[((size_t)ur * 64 + eu + j) * 8 + o] = u_reg[t][j];
+                commit_opad(u_lds, ro / O, eu, ro % O, u_reg[t]);
             }
         }
         for (int i = tid + UUD * NT; i < UTOTd; i += NT) {   // unstaged tail
             int ro = i >> 3, eu = (i & 7) * 8;
-            const __bf16* src = Ut + ((size_t)(cb * 32 + ro / O) * O + (ro % O)) * E + e0 + eu;
-            bf16x8 v;
-            if (e0 + eu + 8 <= E) v = *reinterpret_cast<const bf16x8*>(src);
-            else { for (int j = 0; j < 8; ++j) v[j] = (e0 + eu + j < E) ? src[j] : (__bf16)0.f; }
-            const int ur = ro / O, o = ro % O;
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                u_lds[((size_t)ur * 64 + eu + j) * 8 + o] = v[j];
+            bf16x8 v = load_edges8(Ut + ((size_t)(cb * 32 + ro / O) * O + (ro % O)) * E,
+                                   e0 + eu, E);
+            commit_opad(u_lds, ro / O, eu, ro % O, v);
         }
         if (cb + 1 < nuc) load_u(cb + 1);
         for (int mb = mb_lo; mb < mb_hi; ++mb) {
             // commit the staged g tile, scattered to [m][e][o(pad 8)]
             if (tid < GTOT) {
                 int ro = tid >> 3, eu = (tid & 7) * 8;
-                const int mr = ro / O, o = ro % O;
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    g_lds[((size_t)mr * 64 + eu + j) * 8 + o] = g_reg[j];
+                commit_opad(g_lds, ro / O, eu, ro % O, g_reg);
             }
             load_g(mb + 1 < mb_hi ? mb + 1 : mb_lo);   // next mb (or next cb's first)
             __syncthreads();
@@ -264,6 +230,10 @@ pairconv_bwd_dw_kernel(const __bf16* __restrict__ Gt,  // (mo, O, E)
     bf16x8 u_reg[UU], g_reg[GU], h_reg;
     const int nec = (E + 31) / 32;
 
+    // The edge-guarded loads here and in du are spelled out, not
+    // load_edges8: with the helper the compiler schedules these two kernels
+    // differently and they measured slower (dw +1.3 % at O=5, du +4.6 % /
+    // +6 %; profiles/pairconv_prune.md). fwd and dh are indifferent to it.
     auto load_chunk = [&](int ec) {
         const int e0 = ec * 32;
 #pragma unroll
@@ -367,12 +337,14 @@ pairconv_bwd_dw_kernel(const __bf16* __restrict__ Gt,  // (mo, O, E)
 
 // ---------------------------------------------------------------------------
 // B3: du[c,o,e] = sum_mo R[e,(mo,c)] g[e,mo,o],  R = H @ W^T + bias
-// block: 64 e x 32 urow, loops mo in blocks of 8; R tile recomputed by MFMA
-// exactly as the forward kernel, bounced through LDS, contracted vs g.
+// block: 64 e x 32 urow, loops mo in blocks of 8; the R tile is recomputed by
+// the forward's MFMA loop (mfma_rtile), bounced through LDS, contracted vs g.
+// No W prefetch here: the contraction phase holds more live state than the
+// forward's epilogue, and prefetching under the 2-blocks/CU cap spilled
+// 116-240 B/lane (profiles/LADDER.md).
 // ---------------------------------------------------------------------------
-template <int O, int WP>   // WP: prefetch next mo-block's W frags under the
-                           // contraction phase (see pairconv.hip fwd)
-__global__ void __launch_bounds__(NT, 4)   // keep 2 blocks/CU under WP
+template <int O>
+__global__ void __launch_bounds__(NT, 4)   // cap VGPR<=128: 2 blocks/CU
 pairconv_bwd_du_kernel(const __bf16* __restrict__ H,   // (E,128)
                        const __bf16* __restrict__ P,   // packed W as forward
                        const float* __restrict__ bias, // (mo*miF,)
@@ -394,29 +366,12 @@ pairconv_bwd_du_kernel(const __bf16* __restrict__ H,   // (E,128)
     const int l4 = lane >> 4;
     const int wm = wid >> 1;
     const int we = wid & 1;
-    // cohort mapping: concurrently-resident blocks on one XCD share a urow
-    // chunk (the same packed-W column slice stays L2-resident).
-    int eb, cb;
-    if (coh) {
-        int x = blockIdx.x & 7, r = blockIdx.x >> 3;
-        eb = r % nmemb;
-        cb = x + 8 * (r / nmemb);
-    } else {
-        eb = blockIdx.x % nmemb;
-        cb = blockIdx.x / nmemb;
-    }
+    int eb, cb;                       // the cohort shares a urow chunk
+    cohort_map(coh, nmemb, eb, cb);
     const int e0 = eb * 64;
     const int uc0 = cb * 32;          // urow chunk
 
-    // stage H tile swizzled (as forward)
-    for (int i = tid; i < (64 * KDIM) / 8; i += NT) {
-        int e = i >> 4, k16 = i & 15;
-        int dst = e * 256 + ((k16 * 16) ^ ((e & 15) << 4));
-        bf16x8 v;
-        if (e0 + e < E) v = *reinterpret_cast<const bf16x8*>(H + (size_t)(e0 + e) * KDIM + k16 * 8);
-        else v = bf16x8(0);
-        *reinterpret_cast<bf16x8*>(reinterpret_cast<char*>(h_lds) + dst) = v;
-    }
+    stage_h_tile(h_lds, H, e0, E, tid);
     for (int i = tid; i < 32 * O * 64; i += NT) du_acc[i] = 0.f;
 
     // T14 register staging: the next mo-block's g tile + bias chunk load
@@ -426,7 +381,7 @@ pairconv_bwd_du_kernel(const __bf16* __restrict__ H,   // (E,128)
     bf16x8 g_reg;
     float bias_reg;
     auto load_gb = [&](int mb) {
-        if (tid < GTOT) {
+        if (tid < GTOT) {   // spelled out on purpose: see the note in dw
             int ro = tid >> 3, eu = (tid & 7) * 8;
             const __bf16* src = Gt + ((size_t)(mb * 8 + ro / O) * O + (ro % O)) * E + e0 + eu;
             if (e0 + eu + 8 <= E) g_reg = *reinterpret_cast<const bf16x8*>(src);
@@ -444,16 +399,6 @@ pairconv_bwd_du_kernel(const __bf16* __restrict__ H,   // (E,128)
     load_gb(0);
 
     const int nmo = mo / 8;
-    auto pb_of = [&](int mbb) {
-        return P + ((((size_t)mbb * (miF / 32) + cb) * 4 + wm) * 4) * 4 * 64 * 8
-               + (size_t)lane * 8;
-    };
-    bf16x8 a_pre[WP ? 16 : 1];
-    if (WP) {
-#pragma unroll
-        for (int f = 0; f < 16; ++f)
-            a_pre[f] = *reinterpret_cast<const bf16x8*>(pb_of(0) + (size_t)f * 512);
-    }
     __syncthreads();
 
     for (int mb = 0; mb < nmo; ++mb) {
@@ -465,42 +410,13 @@ pairconv_bwd_du_kernel(const __bf16* __restrict__ H,   // (E,128)
         if (tid < 256) bias_lds[tid] = bias_reg;
         if (mb + 1 < nmo) load_gb(mb + 1);   // issue next block's loads early
         __syncthreads();
-        // MFMA R tile: (256n x 64e) like forward
+        // MFMA R tile (256n x 64e), A-fragments straight from the packed W
         f32x4 acc[4][2];
-#pragma unroll
-        for (int mf = 0; mf < 4; ++mf)
-#pragma unroll
-            for (int ef = 0; ef < 2; ++ef) acc[mf][ef] = {0.f, 0.f, 0.f, 0.f};
-        const __bf16* pbase = pb_of(mb);
-#pragma unroll
-        for (int kit = 0; kit < 4; ++kit) {
-            const int k0 = kit * 32 + l4 * 8;
-            bf16x8 a[4], b[2];
-#pragma unroll
-            for (int mf = 0; mf < 4; ++mf) {
-                a[mf] = WP ? a_pre[mf * 4 + kit]
-                           : *reinterpret_cast<const bf16x8*>(
-                                 pbase + ((size_t)mf * 4 + kit) * 64 * 8);
-            }
-#pragma unroll
-            for (int ef = 0; ef < 2; ++ef) {
-                int e = we * 32 + ef * 16 + l15;
-                int byte = e * 256 + ((k0 * 2) ^ ((e & 15) << 4));
-                b[ef] = *reinterpret_cast<const bf16x8*>(reinterpret_cast<char*>(h_lds) + byte);
-            }
-#pragma unroll
-            for (int mf = 0; mf < 4; ++mf)
-#pragma unroll
-                for (int ef = 0; ef < 2; ++ef)
-                    acc[mf][ef] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[mf], b[ef], acc[mf][ef], 0, 0, 0);
-        }
-        if (WP) {   // issue next mo-block's fragment loads under the
-                    // R-bounce + contraction phases below
-            const __bf16* pn = pb_of(mb + 1 < nmo ? mb + 1 : mb);
-#pragma unroll
-            for (int f = 0; f < 16; ++f)
-                a_pre[f] = *reinterpret_cast<const bf16x8*>(pn + (size_t)f * 512);
-        }
+        const __bf16* pbase = P + ((((size_t)mb * (miF / 32) + cb) * 4 + wm) * 4) * 4 * 64 * 8
+                              + (size_t)lane * 8;
+        mfma_rtile(acc, h_lds, we, l15, l4, [&](int mf, int kit) {
+            return load_wfrag(pbase, mf * 4 + kit);
+        });
         // bounce R (+bias) to LDS [256n][64e]
 #pragma unroll
         for (int mf = 0; mf < 4; ++mf)
@@ -540,15 +456,6 @@ pairconv_bwd_du_kernel(const __bf16* __restrict__ H,   // (E,128)
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
-#define DISPATCH_O(O, ...)                                         \
-    switch (O) {                                                   \
-        case 1: { constexpr int kO = 1; __VA_ARGS__; break; }      \
-        case 3: { constexpr int kO = 3; __VA_ARGS__; break; }      \
-        case 5: { constexpr int kO = 5; __VA_ARGS__; break; }      \
-        case 7: { constexpr int kO = 7; __VA_ARGS__; break; }      \
-        default: TORCH_CHECK(false, "unsupported O ", O);          \
-    }
-
 void pairconv_bwd_dh(torch::Tensor Gt, torch::Tensor Ut, torch::Tensor Wt,
                      torch::Tensor dH, int64_t mo_) {
     int E = dH.size(0), mo = (int)mo_, miF = Ut.size(0), O = Ut.size(1);
@@ -560,7 +467,6 @@ void pairconv_bwd_dh(torch::Tensor Gt, torch::Tensor Ut, torch::Tensor Wt,
     int nsplit = (nmo % 16 == 0) ? 16 : ((nmo % 8 == 0) ? 8 : 1);
     while (eblk * nsplit * 2 <= 1024 && nsplit * 2 <= nmo && nmo % (nsplit * 2) == 0)
         nsplit *= 2;
-    int coh = 0;
     const int PS = 4, PE = 128;
     int panels = ((eblk + PE - 1) / PE) * ((nsplit + PS - 1) / PS);
     dim3 grid((long)panels * PS * PE);
@@ -570,7 +476,7 @@ void pairconv_bwd_dh(torch::Tensor Gt, torch::Tensor Ut, torch::Tensor Wt,
                            reinterpret_cast<const __bf16*>(Gt.data_ptr()),
                            reinterpret_cast<const __bf16*>(Ut.data_ptr()),
                            reinterpret_cast<const __bf16*>(Wt.data_ptr()),
-                           dH.data_ptr<float>(), E, mo, miF, nsplit, eblk, coh);
+                           dH.data_ptr<float>(), E, mo, miF, nsplit, eblk);
     });
     hipError_t err = hipGetLastError();
     TORCH_CHECK(err == hipSuccess, "bwd_dh: ", hipGetErrorString(err));
@@ -608,31 +514,16 @@ void pairconv_bwd_du(torch::Tensor H, torch::Tensor W, torch::Tensor bias,
     int ncb = miF / 32;
     int coh = (ncb % 8 == 0) ? 1 : 0;
     dim3 grid(nmemb * ncb);
-    // WP off by default here: du's contraction phase holds more live state
-    // than fwd's epilogue, so the prefetch spills 116-240 B/lane under the
-    // 2-blocks/CU cap (vs fwd's 24-36 B at O=3/5). SE3_DU_WP=1 for A/B.
-    const char* wp_env = getenv("SE3_DU_WP");
     DISPATCH_O(O, {
-        int wp = wp_env ? atoi(wp_env) : 0;
         size_t lds = 49152 + (size_t)((8 * kO * 64 * 2 + 15) & ~15) +
                      (size_t)32 * kO * 64 * 4 + 256 * 4;
-        if (wp) {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(pairconv_bwd_du_kernel<kO, 1>),
-                               grid, dim3(NT), lds, stream,
-                               reinterpret_cast<const __bf16*>(H.data_ptr()),
-                               reinterpret_cast<const __bf16*>(W.data_ptr()),
-                               bias.data_ptr<float>(),
-                               reinterpret_cast<const __bf16*>(Gt.data_ptr()),
-                               dU.data_ptr<float>(), E, mo, miF, nmemb, coh);
-        } else {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(pairconv_bwd_du_kernel<kO, 0>),
-                               grid, dim3(NT), lds, stream,
-                               reinterpret_cast<const __bf16*>(H.data_ptr()),
-                               reinterpret_cast<const __bf16*>(W.data_ptr()),
-                               bias.data_ptr<float>(),
-                               reinterpret_cast<const __bf16*>(Gt.data_ptr()),
-                               dU.data_ptr<float>(), E, mo, miF, nmemb, coh);
-        }
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(pairconv_bwd_du_kernel<kO>),
+                           grid, dim3(NT), lds, stream,
+                           reinterpret_cast<const __bf16*>(H.data_ptr()),
+                           reinterpret_cast<const __bf16*>(W.data_ptr()),
+                           bias.data_ptr<float>(),
+                           reinterpret_cast<const __bf16*>(Gt.data_ptr()),
+                           dU.data_ptr<float>(), E, mo, miF, nmemb, coh);
     });
     hipError_t err = hipGetLastError();
     TORCH_CHECK(err == hipSuccess, "bwd_du: ", hipGetErrorString(err));

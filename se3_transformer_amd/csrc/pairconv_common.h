@@ -1,0 +1,129 @@
+// Building blocks shared by the pairconv kernels (pairconv.hip: forward;
+// pairconv_bwd.hip: dh, dw, du). Everything here is used by at least two of
+// them; what only one kernel needs stays next to that kernel.
+#pragma once
+
+#include <torch/extension.h>
+#include <hip/hip_runtime.h>
+#include <ATen/hip/HIPContext.h>
+
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+typedef __attribute__((ext_vector_type(4))) float f32x4;
+typedef __attribute__((ext_vector_type(2))) float f32x2;
+
+#define KDIM 128   // radial hidden width = GEMM K
+#define NT 512     // threads per block (8 waves) in all four kernels
+
+__device__ __forceinline__ float b2f(__bf16 x) { return (float)x; }
+
+__device__ __forceinline__ f32x2 b2f2(bf16x2 v) {
+    return f32x2{(float)v[0], (float)v[1]};
+}
+
+// 8 consecutive edges e..e+7 of one e-contiguous row (Ut, Gt, Ht rows are
+// E long and in general not 16B aligned): one full vector when the run is
+// inside E, element by element with zero fill across the ragged end.
+// Used by fwd and dh; dw and du keep their own spelling (see the note in
+// pairconv_bwd_dw_kernel).
+__device__ __forceinline__ bf16x8 load_edges8(const __bf16* __restrict__ row,
+                                              int e, int E) {
+    const __bf16* src = row + e;
+    if (e + 8 <= E) return *reinterpret_cast<const bf16x8*>(src);
+    bf16x8 v(0);
+    for (int j = 0; j < 8; ++j)
+        if (e + j < E) v[j] = src[j];
+    return v;
+}
+
+// Scatter 8 edges of (row, o) into an LDS tile laid out [row][64 e][o PADDED
+// to 8], so the consumer reads all o of one (row, e) as a single 16B vector.
+// The pad lanes o in [O, 8) are zeroed once by the caller and never written.
+__device__ __forceinline__ void commit_opad(__bf16* tile, int row, int eu,
+                                            int o, bf16x8 v) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+        tile[((size_t)row * 64 + eu + j) * 8 + o] = v[j];
+}
+
+// Stage the (64 e x 128 k) H tile of edge block e0 into LDS, rows past E
+// zero-filled. The 16B slots of a row are XOR-swizzled by (e & 15) so the
+// MFMA B-fragment reads in mfma_rtile are bank-conflict free.
+__device__ __forceinline__ void stage_h_tile(__bf16* h_lds,
+                                             const __bf16* __restrict__ H,
+                                             int e0, int E, int tid) {
+    for (int i = tid; i < (64 * KDIM) / 8; i += NT) {   // 16B units
+        int e = i >> 4;             // 16 units per row
+        int k16 = i & 15;           // 16B slot
+        int dst = e * 256 + ((k16 * 16) ^ ((e & 15) << 4));
+        bf16x8 v;
+        if (e0 + e < E) {
+            v = *reinterpret_cast<const bf16x8*>(H + (size_t)(e0 + e) * KDIM + k16 * 8);
+        } else {
+            v = bf16x8(0);
+        }
+        *reinterpret_cast<bf16x8*>(reinterpret_cast<char*>(h_lds) + dst) = v;
+    }
+}
+
+// Fragment f (= mf*4 + kit) of one wave's 16 A-fragments in the packed W
+// [mo/8][miF/32][wm4][mf4][kit4][lane64][8]; pbase already includes lane*8.
+__device__ __forceinline__ bf16x8 load_wfrag(const __bf16* pbase, int f) {
+    return *reinterpret_cast<const bf16x8*>(pbase + (size_t)f * 64 * 8);
+}
+
+// R^T tile GEMM: acc = W-fragments (256 n x K=128) @ H tile (K x 64 e).
+// Wave (wm, we) owns n-rows wm*64..+64 (4 frags mf) x e-cols we*32..+32
+// (2 frags ef). afrag(mf, kit) supplies the A operand: straight from global
+// (load_wfrag) or out of a prefetched register array.
+template <class AFrag>
+__device__ __forceinline__ void mfma_rtile(f32x4 (&acc)[4][2], const __bf16* h_lds,
+                                           int we, int l15, int l4, AFrag afrag) {
+#pragma unroll
+    for (int mf = 0; mf < 4; ++mf)
+#pragma unroll
+        for (int ef = 0; ef < 2; ++ef) acc[mf][ef] = f32x4(0.f);
+#pragma unroll
+    for (int kit = 0; kit < 4; ++kit) {
+        const int k0 = kit * 32 + l4 * 8;
+        bf16x8 a[4], b[2];
+#pragma unroll
+        for (int mf = 0; mf < 4; ++mf) a[mf] = afrag(mf, kit);
+#pragma unroll
+        for (int ef = 0; ef < 2; ++ef) {
+            int e = we * 32 + ef * 16 + l15;
+            int byte = e * 256 + ((k0 * 2) ^ ((e & 15) << 4));
+            b[ef] = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const char*>(h_lds) + byte);
+        }
+#pragma unroll
+        for (int mf = 0; mf < 4; ++mf)
+#pragma unroll
+            for (int ef = 0; ef < 2; ++ef)
+                acc[mf][ef] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[mf], b[ef], acc[mf][ef], 0, 0, 0);
+    }
+}
+
+// Block index -> (edge block eb, W-slice group grp). With coh set (the group
+// count is a multiple of 8) blockIdx & 7, which the dispatcher maps to the
+// XCD, picks the group within a cohort of 8: all concurrently-resident
+// blocks on one XCD share a group, so its packed-W slice stays in that XCD's
+// L2 while the edge blocks stream past.
+__device__ __forceinline__ void cohort_map(int coh, int nmemb, int& eb, int& grp) {
+    if (coh) {
+        int x = blockIdx.x & 7, r = blockIdx.x >> 3;
+        eb = r % nmemb;
+        grp = x + 8 * (r / nmemb);
+    } else {
+        eb = blockIdx.x % nmemb;
+        grp = blockIdx.x / nmemb;
+    }
+}
+
+#define DISPATCH_O(O, ...)                                         \
+    switch (O) {                                                   \
+        case 1: { constexpr int kO = 1; __VA_ARGS__; break; }      \
+        case 3: { constexpr int kO = 3; __VA_ARGS__; break; }      \
+        case 5: { constexpr int kO = 5; __VA_ARGS__; break; }      \
+        case 7: { constexpr int kO = 7; __VA_ARGS__; break; }      \
+        default: TORCH_CHECK(false, "unsupported O ", O);          \
+    }

@@ -297,10 +297,6 @@ def get_basis_packed(r_ij: torch.Tensor, max_degree: int, differentiable: bool =
             rel = r_ij.reshape(-1, 3).contiguous()
             E = rel.shape[0]
             if differentiable and rel.requires_grad and torch.is_grad_enabled():
-                if not hasattr(_fused._EXT, 'sh_basis_bwd'):
-                    raise RuntimeError(
-                        'se3_transformer_amd._C lacks sh_basis_bwd; rebuild '
-                        'the extension (python scripts/build_ext.py)')
                 out = _ShBasisFn.apply(rel, qcat, normtab, meta, TOT,
                                        2 * max_degree)
             else:

@@ -18,15 +18,41 @@ import torch
 _EXT = None
 _EXT_ERR = None
 
+# Every entry point the package calls. _load_ext() checks them once, so no
+# caller probes the module again: a stale build is an error at load, not a
+# reason to run eager.
+_ENTRY_POINTS = (
+    'pairconv_fwd', 'pairconv_bwd_dh', 'pairconv_bwd_dw', 'pairconv_bwd_du',
+    'pack_w_both', 'radial_trunk_fwd', 'radial_trunk_bwd',
+    'ubuild_fwd', 'ubuild_bwd_dx', 'ubuild_bwd_db',
+    'sh_basis_fwd', 'sh_basis_bwd', 'knn_graph', 'attn2_fwd', 'attn2_bwd',
+    'norm_se3_nl_fwd', 'norm_se3_nl_bwd', 'norm_se3_gated_max_c',
+    'norm_se3_gated_fwd', 'norm_se3_gated_bwd',
+    'egnn_rel_dist_fwd', 'egnn_rel_dist_bwd',
+    'egnn_htype_update_fwd', 'egnn_htype_update_bwd',
+)
+
+# Channel ceiling of the gated kernels (GATED_MAX_C in csrc/norm_se3.hip):
+# their LDS tile is 16*C bytes per block.
+NORM_GATED_MAX_C = 2048
+
 
 def _load_ext():
     global _EXT, _EXT_ERR
     if _EXT is None and _EXT_ERR is None:
         try:
-            from se3_transformer_amd import _C as ext
-            _EXT = ext
+            from se3_transformer_amd import _C as mod
         except ImportError as e:  # pragma: no cover
             _EXT_ERR = e
+            return None
+        missing = [n for n in _ENTRY_POINTS if not hasattr(mod, n)]
+        if not missing and mod.norm_se3_gated_max_c() != NORM_GATED_MAX_C:
+            missing = [f'norm_se3_gated_max_c() == {NORM_GATED_MAX_C}']
+        if missing:
+            raise RuntimeError(
+                'se3_transformer_amd._C lacks ' + ', '.join(missing)
+                + '; rebuild the extension (python scripts/build_ext.py)')
+        _EXT = mod
     return _EXT
 
 
@@ -88,7 +114,7 @@ class _FusedPairConv(torch.autograd.Function):
         # frees ~36 GB at the headline 18.2B-param config (enables larger
         # neighbor counts before the activation-memory wall).
         lowmem = os.environ.get('SE3_LOWMEM_PACK') == '1'
-        if hip_bwd and not lowmem and hasattr(ext, 'pack_w_both'):
+        if hip_bwd and not lowmem:
             # one-pass pack kernel: W read once, both fragment layouts
             # written; saved for backward so nothing re-packs per step
             Wd = W.detach().contiguous()
@@ -124,13 +150,13 @@ class _FusedPairConv(torch.autograd.Function):
         need_H, need_W, need_b, need_u = ctx.needs_input_grad[:4]
 
         ext = _load_ext()
-        if ext is not None and os.environ.get('SE3_TORCH_BWD') != '1':
+        if os.environ.get('SE3_TORCH_BWD') != '1':
             dH = dW = db = dUt = None
             g_t = g16.permute(1, 2, 0).contiguous()    # (mo, O, E) bf16
             P1 = Pu = None
             if ctx.packed:
                 P1, Pu = Pdh, Pf
-            elif (need_H or need_u) and hasattr(ext, 'pack_w_both'):
+            elif need_H or need_u:
                 # SE3_LOWMEM_PACK path: re-derive both fragment layouts in
                 # one kernel pass from the saved torch-layout W
                 n128 = mo * miF * K
@@ -139,8 +165,6 @@ class _FusedPairConv(torch.autograd.Function):
                 P1 = torch.empty_like(Pu)
                 ext.pack_w_both(W16, Pu, P1, mo)
             if need_H:
-                if P1 is None:
-                    P1 = _pack_w_dh(W16, mo, miF)
                 dH = torch.zeros(E, K, dtype=torch.float32, device=H16.device)
                 ext.pairconv_bwd_dh(g_t, Ut16, P1, dH, mo)
             P1 = None
@@ -159,8 +183,6 @@ class _FusedPairConv(torch.autograd.Function):
             if need_u:
                 dUt = torch.empty(miF, O, E, dtype=torch.float32,
                                   device=H16.device)
-                if Pu is None:
-                    Pu = _pack_w_fwd(W16, mo, miF)
                 ext.pairconv_bwd_du(H16, Pu, b16.float().reshape(-1),
                                     g_t, dUt, mo)
             return dH, dW, db, dUt, None
@@ -224,10 +246,7 @@ class _NormSE3Fn(torch.autograd.Function):
         ext = _load_ext()
         s32 = scale.detach().reshape(-1).float().contiguous()
         out = torch.empty_like(t)
-        if nl == 0:
-            ext.norm_se3_fwd(t, s32, out, eps)
-        else:
-            ext.norm_se3_nl_fwd(t, s32, out, eps, nl)
+        ext.norm_se3_nl_fwd(t, s32, out, eps, nl)
         ctx.save_for_backward(t, s32)
         ctx.eps = eps
         ctx.nl = nl
@@ -241,11 +260,8 @@ class _NormSE3Fn(torch.autograd.Function):
         t, s32 = ctx.saved_tensors
         dt = torch.empty_like(t)
         dscale = torch.zeros_like(s32)
-        if ctx.nl == 0:
-            ext.norm_se3_bwd(t, s32, dout.contiguous(), dt, dscale, ctx.eps)
-        else:
-            ext.norm_se3_nl_bwd(t, s32, dout.contiguous(), dt, dscale,
-                                ctx.eps, ctx.nl)
+        ext.norm_se3_nl_bwd(t, s32, dout.contiguous(), dt, dscale,
+                            ctx.eps, ctx.nl)
         return (dt, dscale.view(ctx.scale_shape).to(ctx.scale_dtype),
                 None, None)
 
@@ -291,24 +307,9 @@ class _NormSE3GatedFn(torch.autograd.Function):
 
 
 def norm_variants_ok() -> bool:
-    """True when the extension carries the identity and gated-scale NormSE3
-    kernels; a stale build is an error, not a reason to run eager."""
-    ext = _load_ext()
-    if ext is None:
-        return False
-    if not (hasattr(ext, 'norm_se3_nl_fwd') and hasattr(ext, 'norm_se3_nl_bwd')
-            and hasattr(ext, 'norm_se3_gated_fwd')
-            and hasattr(ext, 'norm_se3_gated_bwd')):
-        raise RuntimeError(
-            'se3_transformer_amd._C lacks the norm_se3_nl_*/norm_se3_gated_* '
-            'entry points; rebuild the extension '
-            '(python scripts/build_ext.py)')
-    return True
-
-
-# Channel ceiling of the gated kernels (GATED_MAX_C in csrc/norm_se3.hip):
-# their LDS tile is 16*C bytes per block.
-NORM_GATED_MAX_C = 2048
+    """True when the extension, and with it the identity and gated-scale
+    NormSE3 kernels, is loaded."""
+    return ext_available()
 
 
 def norm_se3(t, scale, eps, nonlin='gelu'):
@@ -417,15 +418,7 @@ class _UBuildFn(torch.autograd.Function):
 
 
 def ubuild_ok(B, C, O, I, F) -> bool:
-    ext = _load_ext()
-    if ext is None or not hasattr(ext, 'ubuild_fwd'):
-        return False
-    if B.requires_grad and torch.is_grad_enabled():
-        if not hasattr(ext, 'ubuild_bwd_db'):
-            raise RuntimeError(
-                'se3_transformer_amd._C lacks ubuild_bwd_db; rebuild the '
-                'extension (python scripts/build_ext.py)')
-    return (B.dtype == torch.float32
+    return (ext_available() and B.dtype == torch.float32
             and C % 32 == 0 and O * I * F <= 343)
 
 
@@ -503,8 +496,7 @@ def htype_update(ht, idx, w, scale, bias, eps):
 
 
 def egnn_kernels_ok(m: int) -> bool:
-    ext = _load_ext()
-    return (ext is not None and hasattr(ext, 'egnn_htype_update_fwd')
+    return (ext_available()
             and m <= 7 and os.environ.get('SE3_EAGER_EGNN') != '1')
 
 
@@ -512,9 +504,8 @@ RADIAL_TRUNK_DIMS = (1, 2, 3, 5, 9, 17, 21, 25)   # instantiated in csrc/radial.
 
 
 def radial_trunk_ok(in_dim: int, mid_dim: int) -> bool:
-    ext = _load_ext()
     return (mid_dim == 128 and in_dim in RADIAL_TRUNK_DIMS
-            and ext is not None and hasattr(ext, 'radial_trunk_fwd'))
+            and ext_available())
 
 
 class _RadialTrunkFn(torch.autograd.Function):
