@@ -4,8 +4,17 @@
 // kernel. One wave per query node: each lane keeps a sorted top-L list of
 // its strided j-candidates in LDS (L = min(k, ceil(n/64)) — a lane can
 // never contribute more than its own candidate count), then the 64 lists
-// are merged with a k-round cross-lane argmin; the k winners' relative
-// geometry and validity mask are written directly.
+// are merged across lanes: a round takes every list head below the wave-wide
+// minimum of the lists' second entries (about ten winners per round on
+// random points), falls back to a single cross-lane argmin on a tie, and
+// the merge stops as soon as no lane has a candidate left; the k winners'
+// relative geometry and validity mask are written directly, 64 slots per
+// pass.
+//
+// Any 1 <= k <= n-1 is served. The only ceiling is the block's dynamic LDS,
+// L*64*8 bytes of lists plus 4*k of winners, which has to fit the
+// KNN_MAX_LDS_BYTES a launch gets without raising the kernel's LDS
+// attribute: at k = n-1 that is ~12 bytes per point, n up to ~5400.
 //
 // Selection semantics match the eager path exactly (:1250-1283):
 //   * self excluded; causal keeps only j < i (overrides everything);
@@ -23,7 +32,9 @@
 #include <hip/hip_runtime.h>
 #include <ATen/hip/HIPContext.h>
 
-#define MAXK2 64
+// dynamic LDS a launch may ask for without hipFuncSetAttribute; mirrored by
+// KNN_MAX_LDS in ops/fused.py and checked against it on first use
+#define KNN_MAX_LDS_BYTES 65536
 
 __global__ void __launch_bounds__(64)
 knn_kernel(const float* __restrict__ coors,        // (b, n, 3)
@@ -38,7 +49,7 @@ knn_kernel(const float* __restrict__ coors,        // (b, n, 3)
     extern __shared__ __attribute__((aligned(8))) char smem[];
     float* ld = reinterpret_cast<float*>(smem);            // [L][64]
     int* li = reinterpret_cast<int*>(smem + (size_t)L * 64 * 4); // [L][64]
-    __shared__ int sel[MAXK2];
+    int* sel = reinterpret_cast<int*>(smem + (size_t)L * 64 * 8); // [k]
 
     const int lane = threadIdx.x & 63;
     const long q = blockIdx.x;                   // query row = bi*n + i
@@ -76,29 +87,65 @@ knn_kernel(const float* __restrict__ coors,        // (b, n, 3)
         if (cnt < L) ++cnt;
     }
 
-    // merge the 64 sorted lists: k rounds of cross-lane argmin over heads
+    // merge the 64 sorted lists into sel[0..k) in (eff, lane) order. A round
+    // takes every head that lies below t, the wave-wide minimum of the
+    // lists' SECOND entries: nothing behind a head is smaller than t, so
+    // those heads are exactly the next winners, and each one's slot is its
+    // rank among them. When no head is below t (the smallest head ties with
+    // t, or nothing is left) the round falls back to one cross-lane argmin
+    // over the heads, which takes one winner or ends the merge. Every branch
+    // below is wave-uniform; each round adds at least one winner or breaks.
     int head = 0;
-    for (int r = 0; r < k; ++r) {
+    int r = 0;
+    while (r < k) {
         float v = (head < cnt) ? ld[(size_t)head * 64 + lane] : 3.0e38f;
-        int l = lane;
+        float t = (head + 1 < cnt) ? ld[(size_t)(head + 1) * 64 + lane] : 3.0e38f;
 #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            float ov = __shfl_xor(v, off);
-            int ol = __shfl_xor(l, off);
-            if (ov < v || (ov == v && ol < l)) { v = ov; l = ol; }
+        for (int off = 32; off > 0; off >>= 1) t = fminf(t, __shfl_xor(t, off));
+        const bool win = v < t;
+        unsigned long long winners = __ballot(win);
+        if (winners == 0ull) {
+            int l = lane;
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                float ov = __shfl_xor(v, off);
+                int ol = __shfl_xor(l, off);
+                if (ov < v || (ov == v && ol < l)) { v = ov; l = ol; }
+            }
+            // v is wave-uniform after the butterfly. The sentinel means no
+            // candidate is left anywhere (causal rows, rows thinned by
+            // `allow`, k = n-1 past the real candidates): every later round
+            // would find the same, so stop; the rest is marked invalid below.
+            if (!(v < 3.0e38f)) break;
+            if (lane == l) {
+                sel[r] = li[(size_t)head * 64 + lane];
+                ++head;
+            }
+            ++r;
+            continue;
         }
-        if (lane == l) {
-            // v == +inf means no candidate anywhere (e.g. causal row 0):
-            // emit -1 so the slot comes out invalid.
-            sel[r] = (v < 3.0e38f) ? li[(size_t)head * 64 + lane] : -1;
+        const int nwin = __popcll(winners);
+        int rank = 0;
+        while (winners) {
+            const int s = __ffsll(winners) - 1;
+            winners &= winners - 1;
+            const float vs = __int_as_float(
+                __builtin_amdgcn_readlane(__float_as_int(v), s));
+            rank += (vs < v || (vs == v && s < lane)) ? 1 : 0;
+        }
+        if (win) {
+            if (r + rank < k) sel[r + rank] = li[(size_t)head * 64 + lane];
             ++head;
         }
+        r += nwin;
     }
+    if (r > k) r = k;
+    for (int s = r + lane; s < k; s += 64) sel[s] = -1;
     __builtin_amdgcn_wave_barrier();
 
-    // lanes 0..k-1: write the selected neighbors' geometry + validity
-    if (lane < k) {
-        int j = sel[lane];
+    // write the selected neighbors' geometry + validity, 64 slots per pass
+    for (int s = lane; s < k; s += 64) {
+        int j = sel[s];
         bool valid = j >= 0;
         if (!valid) j = (i == 0) ? (n > 1 ? 1 : 0) : 0;  // any real node != i
         float dx = 0.f, dy = 0.f, dz = 0.f, d = 0.f;
@@ -110,7 +157,7 @@ knn_kernel(const float* __restrict__ coors,        // (b, n, 3)
             d = sqrtf(dx * dx + dy * dy + dz * dz);
             sp = srow && srow[j];
         }
-        long o = q * k + lane;
+        long o = q * k + s;
         out_idx[o] = j;
         out_dist[o] = d;
         out_rel[o * 3] = dx;
@@ -131,6 +178,8 @@ static const unsigned char* knn_opt_u8(const torch::Tensor& t) {
     return nullptr;
 }
 
+int64_t knn_max_lds_bytes() { return KNN_MAX_LDS_BYTES; }
+
 void knn_graph(torch::Tensor coors, torch::Tensor nmask, torch::Tensor allow,
                torch::Tensor sparse, torch::Tensor idx,
                torch::Tensor dist, torch::Tensor rel, torch::Tensor m,
@@ -138,13 +187,20 @@ void knn_graph(torch::Tensor coors, torch::Tensor nmask, torch::Tensor allow,
     TORCH_CHECK(coors.is_cuda() && coors.dtype() == torch::kFloat32 &&
                 coors.is_contiguous());
     int b = coors.size(0), n = coors.size(1);
-    TORCH_CHECK(k >= 1 && k <= MAXK2 && k <= n - 1);
+    TORCH_CHECK(k >= 1 && k <= n - 1, "knn_graph: need 1 <= k <= n-1, got n=",
+                n, " k=", k);
     TORCH_CHECK(idx.is_contiguous() && dist.is_contiguous() &&
                 rel.is_contiguous() && m.is_contiguous());
+    TORCH_CHECK(idx.numel() == (int64_t)b * n * k && dist.numel() == idx.numel() &&
+                m.numel() == idx.numel() && rel.numel() == 3 * idx.numel(),
+                "knn_graph: outputs must be (b,n,k) / (b,n,k,3)");
     int L = (int)std::min<long>(k, (n + 63) / 64);
+    size_t lds = (size_t)L * 64 * 8 + 4 * (size_t)k;
+    TORCH_CHECK(lds <= KNN_MAX_LDS_BYTES, "knn_graph: n=", n, " k=", k,
+                " needs ", lds, " bytes of LDS per block, the limit is ",
+                KNN_MAX_LDS_BYTES);
     auto stream = at::cuda::getCurrentHIPStream();
     dim3 grid((long)b * n);
-    size_t lds = (size_t)L * 64 * 8;
     hipLaunchKernelGGL(knn_kernel, grid, dim3(64), lds, stream,
                        coors.data_ptr<float>(), knn_opt_u8(nmask),
                        knn_opt_u8(allow), knn_opt_u8(sparse),

@@ -271,6 +271,7 @@ void knn_graph(torch::Tensor coors, torch::Tensor nmask, torch::Tensor allow,
                torch::Tensor sparse, torch::Tensor idx,
                torch::Tensor dist, torch::Tensor rel, torch::Tensor m,
                int64_t k, double radius, bool causal);
+int64_t knn_max_lds_bytes();
 void attn2_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                torch::Tensor mask, torch::Tensor qf, torch::Tensor kf,
                torch::Tensor out, torch::Tensor lse,
@@ -338,6 +339,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("pairconv_bwd_dw", &pairconv_bwd_dw, "dW backward");
     m.def("pairconv_bwd_du", &pairconv_bwd_du, "dU backward");
     m.def("knn_graph", &knn_graph, "on-device kNN graph build");
+    m.def("knn_max_lds_bytes", &knn_max_lds_bytes,
+          "dynamic-LDS ceiling of the kNN kernel (bounds n and k)");
     m.def("attn2_fwd", &attn2_fwd,
           "fused neighbor attention fwd (online softmax, in-kernel rotary)");
     m.def("attn2_bwd", &attn2_bwd, "fused neighbor attention backward");

@@ -314,12 +314,15 @@ class SE3Transformer(nn.Module):
         # eager path's advisory print when neighbor_mask exceeds
         # `neighbors` is skipped here.) Under differentiable_coors the
         # kernel still does the selection and the geometry is re-derived
-        # from its indices below; f64 coordinates, k > 64 and
-        # SE3_EAGER_KNN=1 stay on the eager branch.
+        # from its indices below. The kernel takes any 1 <= k <= n-1 that
+        # fits its LDS budget (fused.knn_ok: k = n-1 up to n ~ 5400), so
+        # the default num_neighbors=inf and radius graphs are served too;
+        # f64 coordinates, SE3_EAGER_KNN=1 and an (n, k) past the LDS
+        # budget stay on the eager branch.
         from ..ops import fused as _fusedmod
         k_total = int(min(neighbors + num_sparse_neighbors, n - 1))  # neighbors may be inf
         use_knn = (coors.is_cuda and coors.dtype == torch.float32
-                   and 1 <= k_total <= 64
+                   and _fusedmod.knn_ok(n, k_total)
                    and os.environ.get('SE3_EAGER_KNN') != '1'
                    and _fusedmod.ext_available())
 
@@ -342,10 +345,27 @@ class SE3Transformer(nn.Module):
                               sparse_neighbor_mask)
                 sparse_u8 = full.to(torch.uint8).contiguous()
             radius = float(valid_radius) if neighbors > 0 else 0.0
-            _fusedmod._EXT.knn_graph(coors.contiguous(), node_mask_u8,
-                                     allow_u8, sparse_u8, idx,
-                                     dist, relp, nm, k_eff,
-                                     radius, bool(self.causal))
+            _fusedmod.knn_graph(coors.contiguous(), node_mask_u8,
+                                allow_u8, sparse_u8, idx,
+                                dist, relp, nm, k_eff,
+                                radius, bool(self.causal))
+
+            if os.environ.get('SE3_COMPACT_NEIGHBORS') == '1' \
+                    and not torch.cuda.is_current_stream_capturing():
+                # each row comes out in ascending distance, so with a
+                # radius (or a causal / thinned row) the valid slots sit at
+                # the front: a trailing run of columns that is invalid in
+                # every row contributes nothing downstream and is cut off.
+                # One small reduction + one host read per forward.
+                used = nm.view(-1, k_eff).any(dim=0)
+                last = used * torch.arange(1, k_eff + 1, device=device)
+                k_eff = max(1, int(last.max().item()))
+                if k_eff < k_total:
+                    idx = idx[..., :k_eff].contiguous()
+                    dist = dist[..., :k_eff].contiguous()
+                    nm = nm[..., :k_eff].contiguous()
+                    relp = relp[:, :, :k_eff].contiguous()
+
             neighbor_indices = idx
             neighbor_rel_dist = dist
             neighbor_rel_pos = relp

@@ -25,7 +25,8 @@ _ENTRY_POINTS = (
     'pairconv_fwd', 'pairconv_bwd_dh', 'pairconv_bwd_dw', 'pairconv_bwd_du',
     'pack_w_both', 'radial_trunk_fwd', 'radial_trunk_bwd',
     'ubuild_fwd', 'ubuild_bwd_dx', 'ubuild_bwd_db',
-    'sh_basis_fwd', 'sh_basis_bwd', 'knn_graph', 'attn2_fwd', 'attn2_bwd',
+    'sh_basis_fwd', 'sh_basis_bwd', 'knn_graph', 'knn_max_lds_bytes',
+    'attn2_fwd', 'attn2_bwd',
     'norm_se3_nl_fwd', 'norm_se3_nl_bwd', 'norm_se3_gated_max_c',
     'norm_se3_gated_fwd', 'norm_se3_gated_bwd',
     'egnn_rel_dist_fwd', 'egnn_rel_dist_bwd',
@@ -35,6 +36,13 @@ _ENTRY_POINTS = (
 # Channel ceiling of the gated kernels (GATED_MAX_C in csrc/norm_se3.hip):
 # their LDS tile is 16*C bytes per block.
 NORM_GATED_MAX_C = 2048
+
+# Dynamic-LDS ceiling of the kNN kernel (KNN_MAX_LDS_BYTES in csrc/knn.hip):
+# what a launch gets without raising the kernel's LDS attribute. A block
+# holds 64 sorted lists of L = min(k, ceil(n/64)) (distance, index) pairs
+# plus the k winners.
+KNN_MAX_LDS = 65536
+_KNN_BUDGET_CHECKED = False
 
 
 def _load_ext():
@@ -68,6 +76,35 @@ def require_ext():
             'se3_transformer_amd._C HIP extension is not built but a GPU is '
             'present; run `python scripts/build_ext.py` '
             f'(import error: {_EXT_ERR})')
+
+
+def knn_lds_bytes(n: int, k: int) -> int:
+    return min(k, -(-n // 64)) * 64 * 8 + 4 * k
+
+
+def knn_ok(n: int, k: int) -> bool:
+    """True when the kNN kernel serves (n, k): any 1 <= k <= n-1 whose LDS
+    footprint fits KNN_MAX_LDS (k = n-1 up to n ~ 5400). Pure Python, the
+    extension is not needed to ask."""
+    return 1 <= k <= n - 1 and knn_lds_bytes(n, k) <= KNN_MAX_LDS
+
+
+def knn_graph(coors, nmask, allow, sparse, idx, dist, rel, m, k, radius,
+              causal):
+    """csrc/knn.hip. The first call checks KNN_MAX_LDS against the built
+    kernel's knn_max_lds_bytes(): knn_ok() must gate on the budget the
+    kernel enforces, so a stale build is an error, not a wrong gate."""
+    global _KNN_BUDGET_CHECKED
+    ext = _load_ext()
+    if not _KNN_BUDGET_CHECKED:
+        if ext.knn_max_lds_bytes() != KNN_MAX_LDS:
+            raise RuntimeError(
+                'se3_transformer_amd._C lacks knn_max_lds_bytes() == '
+                f'{KNN_MAX_LDS}; rebuild the extension '
+                '(python scripts/build_ext.py)')
+        _KNN_BUDGET_CHECKED = True
+    ext.knn_graph(coors, nmask, allow, sparse, idx, dist, rel, m, k, radius,
+                  causal)
 
 
 def fused_shapes_ok(mo: int, miF: int, O: int, mid_dim: int) -> bool:
