@@ -21,6 +21,15 @@
 //   out     (R, DM) f32;  lse (R,) f32 saved for backward
 // One wave per query row; lane j <-> key j within each 64-key tile; the
 // DM axis cycles over lanes in DT chunks of 64.
+//
+// Masked keys: a masked logit is the fill A2_FILL, as the eager path's
+// masked_fill(~mask, -finfo.max) before the softmax. In a row with at
+// least one attended key a masked key has weight exactly 0. A row whose J
+// keys are ALL masked has uniform weights 1/J: out is the plain mean of
+// v, and it is represented by lse[r] == A2_FILL (no attended row can reach
+// that value). The backward then gives dv_j = g/J and dq = dk_j = 0: a
+// masked key never passes gradient to q or k, in any row, because no
+// gradient passes the fill.
 
 #include <torch/extension.h>
 #include <hip/hip_runtime.h>
@@ -28,6 +37,7 @@
 #include <hip/hip_bf16.h>
 
 #define NTA2 256  // 4 waves (= 4 query rows) per block
+#define A2_FILL (-3.0e38f)  // logit of a masked key; lse of an all-masked row
 
 // rotary pairing of se3 rotary.py rotate_half (reference rotary.py:15-24):
 //   out[d] = t[d] cos(f[d]) + sgn(d) * t[P(d)] sin(f[d])
@@ -84,7 +94,7 @@ attn2_fwd_kernel(const T* __restrict__ q, const T* __restrict__ k,
         qv[0] = rope_apply<false>(qv[0], lane, rot, f, 0.f);
     }
 
-    float m = -3.0e38f, s = 0.f;
+    float m = A2_FILL, s = 0.f;
     float ov[DT];
 #pragma unroll
     for (int t = 0; t < DT; ++t) ov[t] = 0.f;
@@ -93,7 +103,7 @@ attn2_fwd_kernel(const T* __restrict__ q, const T* __restrict__ k,
         const int tj = min(64, J - j0);
         // key rotary freq for THIS lane's key (lane j <-> key j0+lane)
         // logits: lane j holds logit for key j0+j
-        float logit = -3.0e38f;
+        float logit = A2_FILL;
         for (int jj = 0; jj < tj; ++jj) {
             const int j = j0 + jj;
             float kfre = 0.f;
@@ -114,11 +124,11 @@ attn2_fwd_kernel(const T* __restrict__ q, const T* __restrict__ k,
             for (int off = 32; off > 0; off >>= 1)
                 part += __shfl_xor(part, off);
             float l = part * scale;
-            if (mrow != nullptr && mrow[j] == 0) l = -3.0e38f;
+            if (mrow != nullptr && mrow[j] == 0) l = A2_FILL;
             if (lane == jj) logit = l;
         }
         // online softmax update over this tile
-        float tm = (lane < tj) ? logit : -3.0e38f;
+        float tm = (lane < tj) ? logit : A2_FILL;
         float mx = tm;
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1)
@@ -160,7 +170,11 @@ attn2_fwd_kernel(const T* __restrict__ q, const T* __restrict__ k,
         int d = t * 64 + lane;
         if (d < DM) out[r * DM + d] = ov[t] * inv_s;
     }
-    if (lane == 0 && lse != nullptr) lse[r] = m + __logf(s);
+    // all J keys masked: m never left the fill, s == J, out = mean of v.
+    // The saved lse is the fill itself (m + log J rounds back to it in
+    // fp32; stored explicitly so the backward can test for it).
+    if (lane == 0 && lse != nullptr)
+        lse[r] = (m == A2_FILL) ? A2_FILL : m + __logf(s);
 }
 
 // ---------------------------------------------------------------------------
@@ -192,6 +206,8 @@ attn2_bwd_kernel(const T* __restrict__ q, const T* __restrict__ k,
     const long kvr = kv_one ? bi : r;
     const unsigned char* mrow = mask ? mask + bi * J : nullptr;
     const float l_row = lse[r];
+    // weight of a masked key: 1/J in an all-masked row (header), else 0
+    const float a_masked = (l_row == A2_FILL) ? 1.f / (float)J : 0.f;
 
     float qv[DT], gv[DT], dqv[DT];
     float delta = 0.f;
@@ -238,10 +254,11 @@ attn2_bwd_kernel(const T* __restrict__ q, const T* __restrict__ k,
             part += __shfl_xor(part, off);
             gvdot += __shfl_xor(gvdot, off);
         }
-        float sim = part * scale;
-        if (masked) sim = -3.0e38f;
-        const float aj = __expf(sim - l_row);
-        const float dsj = aj * (gvdot - delta) * scale;
+        // masked key: weight 0, or 1/J in an all-masked row; never a ds
+        // (the product is rounded on its own, as the forward's logit is)
+        const float sim = __fmul_rn(part, scale);
+        const float aj = masked ? a_masked : __expf(sim - l_row);
+        const float dsj = masked ? 0.f : aj * (gvdot - delta) * scale;
         // dq accumulation (rotated frame)
 #pragma unroll
         for (int t = 0; t < DT; ++t) dqv[t] = fmaf(dsj, kvv[t], dqv[t]);
