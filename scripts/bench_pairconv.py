@@ -1,7 +1,9 @@
 """Microbenchmark the fused pairconv kernels at headline shapes.
 
 Usage (GPU box):  python scripts/bench_pairconv.py [--pair 3,3]
-Prints per-kernel ms and effective TFLOP/s for fwd, bwd_dh, bwd_dw, bwd_du.
+Prints per-kernel ms and GEMM-equivalent TFLOP/s for fwd, bwd_dh, bwd_dw,
+bwd_du on the o-padded edge-major tensors U (miF, E, OP) / G (mo, E, OP), and
+the times of their two producers, ubuild_fwd and pack_g, separately.
 """
 import argparse
 import os
@@ -48,6 +50,12 @@ def main():
     out = torch.zeros(E, mo, O, device=dev)
     gt = torch.randn(mo, O, E, generator=g, device=dev).to(torch.bfloat16)
     bias = torch.zeros(N, device=dev)
+    # the same seeded values in the layout the kernels read
+    OP = _C.pairconv_opad(O)
+    pad = torch.nn.functional.pad
+    U = pad(Ut.permute(0, 2, 1), (0, OP - O)).contiguous()
+    G = pad(gt.permute(0, 2, 1), (0, OP - O)).contiguous()
+    del Ut
 
     gemm_fl = 2.0 * E * N * K
     epi_fl = 2.0 * E * N * O
@@ -67,31 +75,50 @@ def main():
           f'parity fwd={okf} dh={okd}')
 
     if args.only:
-        fn = {'fwd': lambda: _C.pairconv_fwd(H, P, Ut, out, mo),
-              'dh': lambda: _C.pairconv_bwd_dh(gt, Ut, _pack_w_dh(W, mo, miF),
-                                               torch.zeros(E, K, device=dev), mo),
-              'dw': lambda: _C.pairconv_bwd_dw(gt, Ut, H.t().contiguous(),
-                                               torch.empty(N, K, device=dev), mo),
-              'du': lambda: _C.pairconv_bwd_du(H, P, bias, gt,
-                                               torch.empty(miF, O, E, device=dev), mo)}[args.only]
+        fn = {'fwd': lambda: _C.pairconv_fwd_opad(H, P, U, out, mo),
+              'dh': lambda: _C.pairconv_bwd_dh(G, U, _pack_w_dh(W, mo, miF),
+                                               torch.zeros(E, K, device=dev), mo, O),
+              'dw': lambda: _C.pairconv_bwd_dw(G, U, H.t().contiguous(),
+                                               torch.empty(N, K, device=dev), mo, O),
+              'du': lambda: _C.pairconv_bwd_du(H, P, bias, G,
+                                               torch.empty(miF, E, OP, device=dev),
+                                               mo, O)}[args.only]
         print(args.only, timeit(fn, iters=3, warmup=1), 'ms')
         return
-    ms = timeit(lambda: _C.pairconv_fwd(H, P, Ut, out, mo))
+
+    # producers of the padded layout
+    gout = gt.permute(2, 0, 1).float().contiguous()          # (E, mo, O) f32
+    G2 = torch.empty_like(G)
+    ms = timeit(lambda: _C.pack_g(gout, G2))
+    gb = (gout.numel() * 4 + G2.numel() * 2) / 1e9
+    print(f'pack_g      ({di},{do}): {ms:8.3f} ms  {gb/ms:7.2f} TB/s  '
+          f'parity={torch.equal(G2, G)}')
+    del gout, G2
+    I = 2 * di + 1
+    Bb = torch.randn(E, O, I, F, generator=g, device=dev)
+    X = torch.randn(E, mi, I, generator=g, device=dev).to(torch.bfloat16)
+    U2 = torch.empty_like(U)
+    ms = timeit(lambda: _C.ubuild_fwd(Bb, X, U2, O, I, F))
+    gb = (Bb.numel() * 4 + X.numel() * 2 + U2.numel() * 2) / 1e9
+    print(f'ubuild_fwd  ({di},{do}): {ms:8.3f} ms  {gb/ms:7.2f} TB/s')
+    del Bb, X, U2
+
+    ms = timeit(lambda: _C.pairconv_fwd_opad(H, P, U, out, mo))
     print(f'fwd    ({di},{do}): {ms:8.3f} ms  {gemm_fl/ms/1e9:7.1f} TF/s (gemm) '
           f'{(gemm_fl+epi_fl)/ms/1e9:7.1f} TF/s (total)')
 
     P1 = _pack_w_dh(W, mo, miF)
     dH = torch.zeros(E, K, device=dev)
-    ms = timeit(lambda: _C.pairconv_bwd_dh(gt, Ut, P1, dH, mo))
+    ms = timeit(lambda: _C.pairconv_bwd_dh(G, U, P1, dH, mo, O))
     print(f'bwd_dh ({di},{do}): {ms:8.3f} ms  {gemm_fl/ms/1e9:7.1f} TF/s')
 
     Ht = H.t().contiguous()
     dW = torch.empty(N, K, device=dev)
-    ms = timeit(lambda: _C.pairconv_bwd_dw(gt, Ut, Ht, dW, mo))
+    ms = timeit(lambda: _C.pairconv_bwd_dw(G, U, Ht, dW, mo, O))
     print(f'bwd_dw ({di},{do}): {ms:8.3f} ms  {gemm_fl/ms/1e9:7.1f} TF/s')
 
-    dU = torch.empty(miF, O, E, device=dev)
-    ms = timeit(lambda: _C.pairconv_bwd_du(H, P, bias, gt, dU, mo))
+    dU = torch.empty(miF, E, OP, device=dev)
+    ms = timeit(lambda: _C.pairconv_bwd_du(H, P, bias, G, dU, mo, O))
     print(f'bwd_du ({di},{do}): {ms:8.3f} ms  {gemm_fl/ms/1e9:7.1f} TF/s')
 
     # library GEMM reference: the raw R = H @ W^T (what eager must do, without

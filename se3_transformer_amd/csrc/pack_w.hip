@@ -10,14 +10,16 @@
 // ~6% of the round-1 step, r01_final_kernel_stats.csv 'direct_copy' row)
 // with a single kernel: W is read once, both outputs written once.
 //
+// pack_g (below) is the gradient's counterpart: one pass from the autograd
+// layout to the o-padded edge-major layout the backward kernels read.
+//
 // Block = one (m, cb) tile: 32 rows (c) x 128 cols (k), staged in LDS as
 // bf16 with a 16B-slot XOR swizzle so phase-2 reads are conflict-light.
 
 #include <torch/extension.h>
 #include <hip/hip_runtime.h>
 #include <ATen/hip/HIPContext.h>
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+#include "pairconv_common.h"
 
 #define NTP 256
 
@@ -102,4 +104,64 @@ void pack_w_both(torch::Tensor W, torch::Tensor Pf, torch::Tensor Pdh, int64_t m
     }
     hipError_t err = hipGetLastError();
     TORCH_CHECK(err == hipSuccess, "pack_w_both: ", hipGetErrorString(err));
+}
+
+// ---------------------------------------------------------------------------
+// pack_g: grad_out (E, mo, O) f32 -> G (mo, E, OP) bf16, OP = opad_of(O), pad
+// lanes zero, round to nearest even. One (32 e) x (32 mo) tile per block goes
+// through LDS so both sides are coalesced: the read follows the mo*O-long
+// rows of grad_out, the write stores one (m, e) vector per thread with e on
+// the lanes. The odd LDS row length keeps the transposed read conflict-free.
+// ---------------------------------------------------------------------------
+#define PG_E 32
+#define PG_M 32
+
+template <int O>
+__global__ void __launch_bounds__(NTP)
+pack_g_kernel(const float* __restrict__ grad, __bf16* __restrict__ G,
+              int E, int mo) {
+    constexpr int OP = opad_of(O);
+    constexpr int ROW = PG_M * O + 1;
+    __shared__ float tile[PG_E * ROW];
+    const int tid = threadIdx.x;
+    const int e0 = blockIdx.x * PG_E, m0 = blockIdx.y * PG_M;
+    const int mw = (mo - m0 < PG_M) ? mo - m0 : PG_M;
+
+    for (int t = tid; t < PG_E * PG_M * O; t += NTP) {
+        int e = t / (PG_M * O), j = t % (PG_M * O);
+        if (e0 + e < E && j < mw * O)
+            tile[e * ROW + j] = grad[((size_t)(e0 + e) * mo + m0) * O + j];
+    }
+    __syncthreads();
+    for (int t = tid; t < PG_M * PG_E; t += NTP) {
+        int e = t % PG_E, m = t / PG_E;
+        if (e0 + e < E && m < mw) {
+            __bf16 v[OP];
+#pragma unroll
+            for (int o = 0; o < OP; ++o)
+                v[o] = (o < O) ? (__bf16)tile[e * ROW + m * O + o] : (__bf16)0.f;
+            __bf16* dst = G + ((size_t)(m0 + m) * E + e0 + e) * OP;
+            if constexpr (OP == 1) dst[0] = v[0];
+            else *reinterpret_cast<typename OVec<OP>::type*>(dst) =
+                     *reinterpret_cast<typename OVec<OP>::type*>(v);
+        }
+    }
+}
+
+void pack_g(torch::Tensor grad, torch::Tensor G) {
+    TORCH_CHECK(grad.is_cuda() && grad.is_contiguous() &&
+                grad.dtype() == torch::kFloat32 && grad.dim() == 3);
+    int E = grad.size(0), mo = grad.size(1), O = grad.size(2);
+    TORCH_CHECK(O == 1 || O == 3 || O == 5 || O == 7, "unsupported O ", O);
+    TORCH_CHECK(G.is_cuda() && G.is_contiguous() && G.dtype() == torch::kBFloat16 &&
+                G.dim() == 3 && G.size(0) == mo && G.size(1) == E &&
+                G.size(2) == opad_of(O), "expect G as (mo, E, OP(O))");
+    if (E == 0 || mo == 0) return;
+    auto stream = at::cuda::getCurrentHIPStream();
+    dim3 grid((E + PG_E - 1) / PG_E, (mo + PG_M - 1) / PG_M);
+    DISPATCH_O(O, hipLaunchKernelGGL(HIP_KERNEL_NAME(pack_g_kernel<kO>), grid,
+                                     dim3(NTP), 0, stream, grad.data_ptr<float>(),
+                                     reinterpret_cast<__bf16*>(G.data_ptr()), E, mo));
+    hipError_t err = hipGetLastError();
+    TORCH_CHECK(err == hipSuccess, "pack_g: ", hipGetErrorString(err));
 }

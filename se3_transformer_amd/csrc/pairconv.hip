@@ -17,13 +17,15 @@
 //   H   (E, 128)      bf16   radial trunk activations (k-contiguous)
 //   P   (mo*miF*128)  bf16   net.6 weight packed in MFMA A-fragment order
 //                            [mo/8][miF/32][wm4][mf4][kit4][lane64][8]
-//   Ut  (miF, O, E)   bf16   basis-contracted features, e-contiguous
+//   U   (miF, E, OP)  bf16   basis-contracted features, edge-major with o
+//                            padded to OP(O) (pairconv_common.h), pads zero
 //   out (E, mo, O)    f32    pre-initialized with the bias term; kernel adds
 //
 // Tile: block = 512 threads (8 waves) owns (64 edges) x (8*MB2 mo). The H
 // tile is staged to LDS once. The block then loops over miF in chunks of 32:
-// the chunk's u tile goes global -> LDS directly (the co-resident block
-// covers its latency; a register pipeline for it measured slower), and for
+// the chunk's u tile goes global -> LDS as a straight vector copy (the
+// co-resident block covers its latency; a register pipeline for it measured
+// slower), and for
 // each of the MB2 mo-sub-blocks in turn an MFMA GEMM of (256 n-rows x 64
 // e-cols, K=128), n = 8mo x 32urow, is followed by a VALU contraction
 // against u_lds into per-lane accumulators, a cross-lane reduce and an add
@@ -42,27 +44,33 @@
 // while keeping 2-blocks/CU residency: the two sub-blocks run serially, so
 // the MFMA accumulator registers are reused, only the LDS `part` doubles
 // (O=7: 16K h + 32K u + 28K part = 76 KiB <= 80 KiB per block).
+// LP = o width of the LDS u tile: OP(O), except that O=1 keeps its scatter
+// into 8-wide slots (its global layout has no vectors to copy).
+template <int O> struct FwdLP { static constexpr int v = (O == 1) ? 8 : opad_of(O); };
+
 // WP = W-fragment software pipeline: the next sub-block's 16 A-fragments
 // are prefetched into registers during the current sub-block's epilogue
 // (where the MFMA accumulators are dead), so each MFMA phase starts with
 // its operands already in flight instead of paying a fresh L2/HBM round
 // trip.
-template <int O, int MB2, int WP>
+template <int O, int MB2, int WP, int UNR>
 __global__ void __launch_bounds__(NT, 4)   // cap VGPR<=128: 2 blocks/CU
 pairconv_fwd_kernel(const __bf16* __restrict__ H,
                     const __bf16* __restrict__ P,
-                    const __bf16* __restrict__ Ut,
+                    const __bf16* __restrict__ Ut,   // (miF, E, OP)
                     float* __restrict__ out,
                     int E, int mo, int miF, int nmemb, int coh) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // carve: H tile | u chunk | partial accumulator. The u chunk is stored
-    // [urow][e][o] with o PADDED to 8 so the epilogue reads one 16B vector
-    // per (urow, e) instead of O scalar ds_read_u16s — the epilogue VALU/LDS
-    // issue rate was co-limiting with the MFMA pipe (measured ~240 TF/s vs
-    // the ~380 TF/s W-stream roofline).
+    // [urow][e][o] with o PADDED to LP, as it is in memory, so the epilogue
+    // reads one vector per (urow, e) instead of O scalar ds_read_u16s — the
+    // epilogue VALU/LDS issue rate was co-limiting with the MFMA pipe
+    // (measured ~240 TF/s vs the ~380 TF/s W-stream roofline).
+    constexpr int LP = FwdLP<O>::v;
+    typedef typename OVec<LP>::type uvec;
     __bf16* h_lds = reinterpret_cast<__bf16*>(smem);                       // [64][128] swizzled, 16 KiB
-    __bf16* u_lds = reinterpret_cast<__bf16*>(smem + 16384);               // [32][64][8] 32 KiB
-    float* part = reinterpret_cast<float*>(smem + 16384 + UCHUNK * BLK_E * 8 * 2); // [64][8*MB2][O]
+    __bf16* u_lds = reinterpret_cast<__bf16*>(smem + 16384);               // [32][64][LP] <= 32 KiB
+    float* part = reinterpret_cast<float*>(smem + 16384 + UCHUNK * BLK_E * LP * 2); // [64][8*MB2][O]
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -78,13 +86,13 @@ pairconv_fwd_kernel(const __bf16* __restrict__ H,
     const int mo0 = mb * BLK_MO * MB2;
 
     stage_h_tile(h_lds, H, e0, E, tid);
-    // zero partial accumulator + the u pad lanes (o in [O, 8) are never
-    // overwritten by staging, so one upfront clear keeps them zero)
     for (int i = tid; i < BLK_E * BLK_MO * MB2 * O; i += NT) part[i] = 0.f;
-    for (int i = tid; i < UCHUNK * BLK_E * 8 / 8; i += NT)
-        *reinterpret_cast<bf16x8*>(u_lds + (size_t)i * 8) = bf16x8(0);
+    if constexpr (O == 1) {   // pad lanes of the scatter slots, cleared once
+        for (int i = tid; i < UCHUNK * BLK_E * 8 / 8; i += NT)
+            *reinterpret_cast<bf16x8*>(u_lds + (size_t)i * 8) = bf16x8(0);
+    }
 
-    constexpr int UTOT = (UCHUNK * O * BLK_E) / 8;   // u chunk in 16B units
+    constexpr int UTOT = (UCHUNK * O * BLK_E) / 8;   // O=1: u chunk in 16B units
     const int nchunks = miF / UCHUNK;
     auto pb_of = [&](int cc, int ss) {
         return P + ((((size_t)(mb * MB2 + ss) * (miF / 32) + cc) * 4 + wm) * 4) * 4 * 64 * 8
@@ -99,13 +107,55 @@ pairconv_fwd_kernel(const __bf16* __restrict__ H,
     __syncthreads();
 
     for (int c = 0; c < nchunks; ++c) {
-        // ---- stage the u chunk, scattered to [urow][e][o(pad 8)]
-        for (int i = tid; i < UTOT; i += NT) {
-            int ro = i >> 3;            // (urow*O + o)
-            int eu = (i & 7) * 8;       // e offset within 64
-            const int ur = ro / O, o = ro % O;
-            bf16x8 v = load_edges8(Ut + ((size_t)(c * UCHUNK + ur) * O + o) * E, e0 + eu, E);
-            commit_opad(u_lds, ur, eu, o, v);
+        // ---- stage the u chunk [urow][e][LP]: one vector per (urow, e),
+        // rows past E zero-filled
+        if constexpr (O == 1) {
+            for (int i = tid; i < UTOT; i += NT) {
+                int ur = i >> 3;            // urow
+                int eu = (i & 7) * 8;       // e offset within 64
+                bf16x8 v = load_edges8(Ut + (size_t)(c * UCHUNK + ur) * E, e0 + eu, E);
+                commit_opad(u_lds, ur, eu, 0, v);
+            }
+        } else {
+            // 16 B units: one edge at LP=8, two at LP=4 (whose rows are
+            // only 8 B aligned when E is odd: the load is declared so).
+            // A wave covers RPW whole urows per pass, so the row base is
+            // wave-uniform (scalar registers) and only the offset inside
+            // the wave's rows is per lane. At LP=8 the wave's row is read
+            // through a buffer resource that ends at the last valid edge
+            // of the block: lanes past E read zeros by the range check, and
+            // the load needs neither a 64-bit per-lane address nor a
+            // predicate. The MFMA and epilogue phases have no vector
+            // register to spare for either.
+            constexpr int EPU = 8 / LP;             // edges per unit
+            constexpr int UPR = BLK_E / EPU;        // units per urow
+            constexpr int RPW = 64 / UPR;           // urows per wave per pass
+            constexpr int RPK = NT / UPR;           // urows per pass of the block
+            const int swid = __builtin_amdgcn_readfirstlane(tid >> 6);
+            const int eu = (lane % UPR) * EPU;
+            const unsigned u_off = ((unsigned)(lane / UPR) * E + eu) * LP * 2;
+            const char* ub = reinterpret_cast<const char*>(
+                Ut + ((size_t)(c * UCHUNK + swid * RPW) * E + e0) * LP);
+#pragma unroll(UNR)
+            for (int k = 0; k < UCHUNK / RPK; ++k) {
+                const char* src = ub + (size_t)k * RPK * E * LP * 2 + u_off;
+                bf16x8 v(0);
+                if constexpr (LP == 8) {
+                    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+                    const int left = E - e0;        // > 0: the block exists
+                    __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+                        const_cast<char*>(ub + (size_t)k * RPK * E * LP * 2), 0,
+                        (left < BLK_E ? left : BLK_E) * 16, 0x00020000);
+                    v = __builtin_bit_cast(
+                        bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)u_off, 0, 0));
+                } else if (e0 + eu + EPU <= E) {
+                    v = *reinterpret_cast<const bf16x8_a8*>(src);
+                } else if (EPU == 2 && e0 + eu < E) {   // last edge of an odd E
+                    bf16x4 lo = *reinterpret_cast<const bf16x4*>(src);
+                    v = bf16x8{lo[0], lo[1], lo[2], lo[3], 0, 0, 0, 0};
+                }
+                *reinterpret_cast<bf16x8*>(u_lds + ((size_t)k * NT + tid) * 8) = v;
+            }
         }
         __syncthreads();
 
@@ -135,15 +185,15 @@ pairconv_fwd_kernel(const __bf16* __restrict__ H,
         }
 
         // ---- epilogue: contract acc against u_lds into s[ef][moi][o-pair].
-        // One ds_read_b128 per (row, e) covers all 8 padded o; the o-pair
+        // One vector read per (row, e) covers all padded o; the o-pair
         // float2 accumulation maps onto v_pk_fma_f32.
-        f32x2 s[2][2][4];
+        f32x2 s[2][2][LP / 2];
 #pragma unroll
         for (int ef = 0; ef < 2; ++ef)
 #pragma unroll
             for (int mi_ = 0; mi_ < 2; ++mi_)
 #pragma unroll
-                for (int p_ = 0; p_ < 4; ++p_) s[ef][mi_][p_] = f32x2{0.f, 0.f};
+                for (int p_ = 0; p_ < LP / 2; ++p_) s[ef][mi_][p_] = f32x2{0.f, 0.f};
 
 #pragma unroll
         for (int mf = 0; mf < 2; ++mf) {   // mf and mf+2 share urow (rows r, r+32)
@@ -156,10 +206,10 @@ pairconv_fwd_kernel(const __bf16* __restrict__ H,
                     const int e = we * 32 + ef * 16 + l15;
                     const float rv0 = acc[mf][ef][reg];
                     const float rv1 = acc[mf + 2][ef][reg];
-                    bf16x8 uv8 = *reinterpret_cast<const bf16x8*>(
-                        u_lds + ((size_t)urow * BLK_E + e) * 8);
+                    uvec uv8 = *reinterpret_cast<const uvec*>(
+                        u_lds + ((size_t)urow * BLK_E + e) * LP);
 #pragma unroll
-                    for (int p_ = 0; p_ < 4; ++p_) {
+                    for (int p_ = 0; p_ < LP / 2; ++p_) {
                         f32x2 u2 = {(float)uv8[2 * p_], (float)uv8[2 * p_ + 1]};
                         s[ef][0][p_] += rv0 * u2;
                         s[ef][1][p_] += rv1 * u2;
@@ -174,7 +224,7 @@ pairconv_fwd_kernel(const __bf16* __restrict__ H,
 #pragma unroll
             for (int mi_ = 0; mi_ < 2; ++mi_)
 #pragma unroll
-                for (int p_ = 0; p_ < 4; ++p_) {
+                for (int p_ = 0; p_ < LP / 2; ++p_) {
 #pragma unroll
                     for (int c2 = 0; c2 < 2; ++c2) {
                         if (2 * p_ + c2 >= O) break;
@@ -219,19 +269,27 @@ pairconv_fwd_kernel(const __bf16* __restrict__ H,
 // (measurements in profiles/LADDER.md):
 //   MB2 = 2 wherever mo allows it — sharing a staged u chunk between two
 //         mo-blocks halves the u traffic.
-//   WP on at O=3,5 (+7% at O=5); at O=7 the held prefetch registers spill
-//         the epilogue (108 B/lane, -9%); O=1 has only been run without it.
+//   WP on at O=5 (+7%, and +4% re-measured on the padded layout); at O=7
+//         the held prefetch registers spill the epilogue (108 B/lane, -9%);
+//         at O=3 the OP=4 epilogue is short enough that the prefetch only
+//         adds spills (84 B/lane) and loses 11%; O=1 has only been run
+//         without it.
+//   UNR = u-staging loads in flight per thread. One at a time at OP=8
+//         (2 and 4 tie or lose and add scratch); both of its two at OP=4,
+//         where the MFMA phases are shortest and the exposed latency shows
+//         (4.13 -> 3.96 ms at (1,1)). profiles/opad_layout.md.
 template <int O, int MB2>
 static void launch_fwd(const torch::Tensor& H, const torch::Tensor& P,
                        const torch::Tensor& Ut, torch::Tensor& out,
                        int E, int mo, int miF) {
-    constexpr int WP = (O == 3 || O == 5) ? 1 : 0;
+    constexpr int WP = (O == 5) ? 1 : 0;
+    constexpr int UNR = (O == 3) ? 2 : 1;
     int nmemb = (E + BLK_E - 1) / BLK_E;
     int ng = mo / (BLK_MO * MB2);
     int coh = (ng % 8 == 0) ? 1 : 0;
-    size_t lds = 16384 + (size_t)UCHUNK * BLK_E * 8 * 2
+    size_t lds = 16384 + (size_t)UCHUNK * BLK_E * FwdLP<O>::v * 2
                  + (size_t)BLK_E * BLK_MO * MB2 * O * 4;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(pairconv_fwd_kernel<O, MB2, WP>),
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(pairconv_fwd_kernel<O, MB2, WP, UNR>),
                        dim3(nmemb * ng), dim3(NT), lds,
                        at::cuda::getCurrentHIPStream(),
                        reinterpret_cast<const __bf16*>(H.data_ptr()),
@@ -240,21 +298,27 @@ static void launch_fwd(const torch::Tensor& H, const torch::Tensor& P,
                        out.data_ptr<float>(), E, mo, miF, nmemb, coh);
 }
 
-void pairconv_fwd(torch::Tensor H, torch::Tensor W, torch::Tensor Ut,
-                  torch::Tensor out, int64_t mo_) {
+int64_t pairconv_opad(int64_t O) { return opad_of((int)O); }
+
+// U is (miF, E, OP(O)) with zero pads; O is out's last dim.
+void pairconv_fwd_opad(torch::Tensor H, torch::Tensor W, torch::Tensor Ut,
+                       torch::Tensor out, int64_t mo_) {
     TORCH_CHECK(H.is_cuda() && W.is_cuda() && Ut.is_cuda() && out.is_cuda());
     TORCH_CHECK(H.dtype() == torch::kBFloat16 && W.dtype() == torch::kBFloat16 &&
                 Ut.dtype() == torch::kBFloat16 && out.dtype() == torch::kFloat32);
     TORCH_CHECK(H.is_contiguous() && W.is_contiguous() && Ut.is_contiguous() &&
                 out.is_contiguous());
+    TORCH_CHECK(Ut.dim() == 3 && out.dim() == 3);
     int E = H.size(0);
     int mo = (int)mo_;
     int miF = Ut.size(0);
-    int O = Ut.size(1);
+    int O = out.size(2);
     TORCH_CHECK(H.size(1) == KDIM, "radial hidden dim must be 128");
     TORCH_CHECK(W.numel() == (int64_t)mo * miF * KDIM, "expect packed W");
-    TORCH_CHECK(Ut.size(2) == E);
-    TORCH_CHECK(out.size(0) == E && out.size(1) == mo && out.size(2) == O);
+    TORCH_CHECK(O == 1 || O == 3 || O == 5 || O == 7, "unsupported O ", O);
+    TORCH_CHECK(Ut.size(1) == E && Ut.size(2) == opad_of(O),
+                "expect U as (miF, E, OP(O))");
+    TORCH_CHECK(out.size(0) == E && out.size(1) == mo);
     TORCH_CHECK(miF % UCHUNK == 0, "miF must be a multiple of 32");
     TORCH_CHECK(mo % BLK_MO == 0, "mo must be a multiple of 8");
     DISPATCH_O(O, {
@@ -263,6 +327,17 @@ void pairconv_fwd(torch::Tensor H, torch::Tensor W, torch::Tensor Ut,
     });
     hipError_t err = hipGetLastError();
     TORCH_CHECK(err == hipSuccess, "pairconv_fwd launch failed: ", hipGetErrorString(err));
+}
+
+// The (miF, O, E) entry kept for callers of the e-contiguous layout: repack
+// to (miF, E, OP) with zero pads, then the kernel above.
+void pairconv_fwd(torch::Tensor H, torch::Tensor W, torch::Tensor Ut,
+                  torch::Tensor out, int64_t mo_) {
+    TORCH_CHECK(Ut.dim() == 3 && out.dim() == 3 && Ut.size(1) == out.size(2));
+    int O = Ut.size(1);
+    TORCH_CHECK(O == 1 || O == 3 || O == 5 || O == 7, "unsupported O ", O);
+    auto U = at::constant_pad_nd(Ut.permute({0, 2, 1}), {0, opad_of(O) - O}).contiguous();
+    pairconv_fwd_opad(H, W, U, out, mo_);
 }
 
 void sh_basis_fwd(torch::Tensor rel, torch::Tensor qcat, torch::Tensor normtab,
@@ -295,14 +370,15 @@ void norm_se3_gated_bwd(torch::Tensor t, torch::Tensor Wt, torch::Tensor gate,
                         torch::Tensor dout, torch::Tensor dt,
                         torch::Tensor dgate, torch::Tensor nu, double eps,
                         int64_t nonlin);
-void pairconv_bwd_dh(torch::Tensor G, torch::Tensor Ut, torch::Tensor Wt,
-                     torch::Tensor dH, int64_t mo_);
-void pairconv_bwd_dw(torch::Tensor G, torch::Tensor Ut, torch::Tensor Ht,
-                     torch::Tensor dW, int64_t mo_);
+void pairconv_bwd_dh(torch::Tensor G, torch::Tensor U, torch::Tensor Wt,
+                     torch::Tensor dH, int64_t mo_, int64_t O_);
+void pairconv_bwd_dw(torch::Tensor G, torch::Tensor U, torch::Tensor Ht,
+                     torch::Tensor dW, int64_t mo_, int64_t O_);
 void pairconv_bwd_du(torch::Tensor H, torch::Tensor W, torch::Tensor bias,
-                     torch::Tensor G, torch::Tensor dU, int64_t mo_);
+                     torch::Tensor G, torch::Tensor dU, int64_t mo_, int64_t O_);
 void pack_w_both(torch::Tensor W, torch::Tensor Pf, torch::Tensor Pdh, int64_t mo_);
-void ubuild_fwd(torch::Tensor B, torch::Tensor X, torch::Tensor Ut,
+void pack_g(torch::Tensor grad, torch::Tensor G);
+void ubuild_fwd(torch::Tensor B, torch::Tensor X, torch::Tensor U,
                 int64_t O, int64_t I, int64_t F);
 void ubuild_bwd_dx(torch::Tensor B, torch::Tensor dU, torch::Tensor dX,
                    int64_t O, int64_t I, int64_t F);
@@ -335,6 +411,11 @@ void radial_trunk_bwd(torch::Tensor dH, torch::Tensor X, torch::Tensor W0,
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("pairconv_fwd", &pairconv_fwd,
           "fused radial-GEMM + basis contraction forward (MI355X)");
+    m.def("pairconv_fwd_opad", &pairconv_fwd_opad,
+          "the same on U in the (miF, E, OP) o-padded edge-major layout");
+    m.def("pairconv_opad", &pairconv_opad, "padded o width OP(O)");
+    m.def("pack_g", &pack_g,
+          "grad_out (E, mo, O) f32 -> G (mo, E, OP) bf16, zero pads");
     m.def("pairconv_bwd_dh", &pairconv_bwd_dh, "dH backward");
     m.def("pairconv_bwd_dw", &pairconv_bwd_dw, "dW backward");
     m.def("pairconv_bwd_du", &pairconv_bwd_du, "dU backward");
@@ -363,7 +444,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("radial_trunk_bwd", &radial_trunk_bwd,
           "fused radial trunk backward");
     m.def("ubuild_fwd", &ubuild_fwd,
-          "basis x features precontraction (e-contiguous out)");
+          "basis x features precontraction, out (C*F, E, OP)");
     m.def("ubuild_bwd_dx", &ubuild_bwd_dx, "ubuild dX backward");
     m.def("ubuild_bwd_db", &ubuild_bwd_db,
           "ubuild dB backward (differentiable coordinates)");

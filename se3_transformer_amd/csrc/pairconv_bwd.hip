@@ -1,14 +1,20 @@
 // Backward kernels for the fused pairwise convolution (see pairconv.hip).
 //
 //   R[e,n]  = H[e,:] . W[n,:] + bias[n],   n = (mo, c),  c = (mi,f) "urow"
-//   out[e,mo,o] = sum_c R[e,(mo,c)] * u[c,o,e]
+//   out[e,mo,o] = sum_c R[e,(mo,c)] * u[c,e,o]
 //
-// Gradients (g = dL/dout, (E,mo,O) bf16):
-//   dR[e,n]   = sum_o g[e,mo,o] * u[c,o,e]          (VALU, recomputed on the fly)
+// u, g and du are o-padded and edge-major (OP = opad_of(O), pads zero):
+//   U (miF, E, OP) bf16 | G (mo, E, OP) bf16 (pack_g) | dU (miF, E, OP) f32
+// so every kernel stages whole (row, edge) vectors with plain copies. At
+// O=1 that layout is the [row][E] the kernels always read, and the O=1
+// instantiations stage as they always did.
+//
+// Gradients (g = dL/dout):
+//   dR[e,n]   = sum_o g[mo,e,o] * u[c,e,o]          (v_dot2, recomputed on the fly)
 //   dH[e,k]   = sum_n dR[e,n] * W[n,k]              (kernel B1, MFMA, needs W^T)
 //   dW[n,k]   = sum_e dR[e,n] * H[e,k]              (kernel B2, MFMA, needs H^T)
-//   db[n]     = sum_e dR[e,n]                       (folded into B2)
-//   du[c,o,e] = sum_mo R[e,(mo,c)] * g[e,mo,o]      (kernel B3, recomputes R)
+//   db[n]     = sum_e dR[e,n]                       (one library GEMM over G and U, ops/fused.py)
+//   du[c,e,o] = sum_mo R[e,(mo,c)] * g[mo,e,o]      (kernel B3, recomputes R)
 //
 // dR / R are never written to global memory anywhere.
 
@@ -23,18 +29,21 @@
 // ---------------------------------------------------------------------------
 template <int O>
 __global__ void __launch_bounds__(NT)
-pairconv_bwd_dh_kernel(const __bf16* __restrict__ Gt,  // (mo, O, E) bf16
-                       const __bf16* __restrict__ Ut,  // (miF, O, E) bf16
+pairconv_bwd_dh_kernel(const __bf16* __restrict__ Gt,  // (mo, E, OP) bf16
+                       const __bf16* __restrict__ Ut,  // (miF, E, OP) bf16
                        const __bf16* __restrict__ P1,  // packed W: [mo/8][miF/32][wk2][kf4][ns8][lane64][8]
                        float* __restrict__ dH,         // (E, 128) f32 (zeroed)
                        int E, int mo, int miF, int nsplit, int nmemb) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    // u/g tiles are [row][e][o PADDED to 8]: the dR build then reads ONE
-    // 16B vector per (row, e) and contracts with v_dot2_f32_bf16 — no
-    // scalar LDS reads, no bf16->f32 conversion ops.
+    // u/g tiles are [row][e][o PADDED to LP], as in memory: the dR build
+    // reads ONE vector per (row, e) and contracts with v_dot2_f32_bf16 — no
+    // scalar LDS reads, no bf16->f32 conversion ops. O=1 scatters its
+    // [row][E] tensors into 8-wide slots.
+    constexpr int LP = (O == 1) ? 8 : opad_of(O);
+    typedef typename OVec<LP>::type ovec;
     __bf16* dr_lds = reinterpret_cast<__bf16*>(smem);                 // [64e][256n] 32 KiB
-    __bf16* u_lds = reinterpret_cast<__bf16*>(smem + 32768);          // [32][64][8] 32 KiB
-    __bf16* g_lds = reinterpret_cast<__bf16*>(smem + 65536);          // [8][64][8] 8 KiB
+    __bf16* u_lds = reinterpret_cast<__bf16*>(smem + 32768);          // [32][64][LP]
+    __bf16* g_lds = u_lds + 32 * 64 * LP;                             // [8][64][LP]
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -65,82 +74,70 @@ pairconv_bwd_dh_kernel(const __bf16* __restrict__ Gt,  // (mo, O, E) bf16
     const int mb_hi = mb_lo + nmo / nsplit;
 
     // T14 register staging: next g tile (every mb) and a slice of the next
-    // u chunk (every cb) load under the dR + MFMA phases.
-    constexpr int GTOT = (8 * O * 64) / 8;     // g tile, 16B units (<= NT)
-    constexpr int UTOTd = (32 * O * 64) / 8;   // u chunk, 16B units
-    constexpr int UUD = 2;                     // staged u units per thread
-    bf16x8 g_reg, u_reg[UUD];
+    // u chunk (every cb) load under the dR + MFMA phases. A staging unit is
+    // one (row, e) vector; at O=1 it is 8 edges of one row.
+    constexpr int GTOT = (O == 1) ? (8 * 64) / 8 : 8 * 64;      // g tile units (<= NT)
+    constexpr int UTOTd = (O == 1) ? (32 * 64) / 8 : 32 * 64;   // u chunk units
+    constexpr int UUD = 16 / LP;               // staged u units per thread (8 VGPRs)
+    ovec g_reg, u_reg[UUD];
+    auto ld_unit = [&](const __bf16* __restrict__ T, int row0, int i) -> ovec {
+        if constexpr (O == 1)
+            return load_edges8(T + (size_t)(row0 + (i >> 3)) * E, e0 + (i & 7) * 8, E);
+        else
+            return load_ovec<LP>(T, (size_t)(row0 + (i >> 6)), e0 + (i & 63), E);
+    };
+    auto st_unit = [&](__bf16* tile, int i, ovec v) {
+        if constexpr (O == 1) commit_opad(tile, i >> 3, (i & 7) * 8, 0, v);
+        else *reinterpret_cast<ovec*>(tile + (size_t)i * LP) = v;
+    };
     auto load_g = [&](int mb) {
-        if (tid < GTOT) {
-            int ro = tid >> 3, eu = (tid & 7) * 8;   // ro = m*O+o
-            g_reg = load_edges8(Gt + ((size_t)(mb * 8 + ro / O) * O + (ro % O)) * E,
-                                e0 + eu, E);
-        }
+        if (tid < GTOT) g_reg = ld_unit(Gt, mb * 8, tid);
     };
     auto load_u = [&](int cb) {
 #pragma unroll
         for (int t = 0; t < UUD; ++t) {
             int i = tid + t * NT;
-            if (i < UTOTd) {
-                int ro = i >> 3, eu = (i & 7) * 8;
-                u_reg[t] = load_edges8(Ut + ((size_t)(cb * 32 + ro / O) * O + (ro % O)) * E,
-                                       e0 + eu, E);
-            }
+            if (i < UTOTd) u_reg[t] = ld_unit(Ut, cb * 32, i);
         }
     };
     load_u(0);
     load_g(mb_lo);
-    // zero the o-pad lanes once (staging never overwrites o in [O, 8))
-    for (int i = tid; i < (32 + 8) * 64; i += NT)
-        *reinterpret_cast<bf16x8*>(u_lds + (size_t)i * 8) = bf16x8(0);
+    if constexpr (O == 1) {   // pad lanes of the scatter slots, cleared once
+        for (int i = tid; i < (32 + 8) * 64; i += NT)
+            *reinterpret_cast<bf16x8*>(u_lds + (size_t)i * 8) = bf16x8(0);
+    }
 
     for (int cb = 0; cb < nuc; ++cb) {
-        // commit the staged u chunk, scattered to [urow][e][o(pad 8)]
+        // commit the staged u chunk [urow][e][LP]
         __syncthreads();
 #pragma unroll
         for (int t = 0; t < UUD; ++t) {
             int i = tid + t * NT;
-            if (i < UTOTd) {
-                int ro = i >> 3, eu = (i & 7) * 8;
-                commit_opad(u_lds, ro / O, eu, ro % O, u_reg[t]);
-            }
+            if (i < UTOTd) st_unit(u_lds, i, u_reg[t]);
         }
-        for (int i = tid + UUD * NT; i < UTOTd; i += NT) {   // unstaged tail
-            int ro = i >> 3, eu = (i & 7) * 8;
-            bf16x8 v = load_edges8(Ut + ((size_t)(cb * 32 + ro / O) * O + (ro % O)) * E,
-                                   e0 + eu, E);
-            commit_opad(u_lds, ro / O, eu, ro % O, v);
-        }
+        for (int i = tid + UUD * NT; i < UTOTd; i += NT)     // unstaged tail
+            st_unit(u_lds, i, ld_unit(Ut, cb * 32, i));
         if (cb + 1 < nuc) load_u(cb + 1);
         for (int mb = mb_lo; mb < mb_hi; ++mb) {
-            // commit the staged g tile, scattered to [m][e][o(pad 8)]
-            if (tid < GTOT) {
-                int ro = tid >> 3, eu = (tid & 7) * 8;
-                commit_opad(g_lds, ro / O, eu, ro % O, g_reg);
-            }
+            // commit the staged g tile [m][e][LP]
+            if (tid < GTOT) st_unit(g_lds, tid, g_reg);
             load_g(mb + 1 < mb_hi ? mb + 1 : mb_lo);   // next mb (or next cb's first)
             __syncthreads();
             // cooperative dR tile [64e][256n]: thread owns (e, run of 8 n);
-            // per n: one 16B g vector (shared over the run) dot one 16B u
-            // vector via 4 v_dot2_f32_bf16; one swizzled b128 write per run.
+            // per n: one g vector (shared over the run) dot one u vector
+            // via LP/2 v_dot2_f32_bf16; one swizzled b128 write per run.
             for (int i = tid; i < (64 * 256) / 8; i += NT) {
                 int e = i & 63, n8 = i >> 6;
                 int m = n8 >> 2;                      // (n8*8)>>5
-                bf16x8 g8 = *reinterpret_cast<const bf16x8*>(
-                    g_lds + ((size_t)m * 64 + e) * 8);
-                const bf16x2* g2 = reinterpret_cast<const bf16x2*>(&g8);
+                ovec g8 = *reinterpret_cast<const ovec*>(
+                    g_lds + ((size_t)m * 64 + e) * LP);
                 __bf16 v0[8];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     int c = (n8 * 8 + j) & 31;
-                    bf16x8 u8 = *reinterpret_cast<const bf16x8*>(
-                        u_lds + ((size_t)c * 64 + e) * 8);
-                    const bf16x2* u2 = reinterpret_cast<const bf16x2*>(&u8);
-                    float acc = 0.f;
-#pragma unroll
-                    for (int p = 0; p < 4; ++p)
-                        acc = __builtin_amdgcn_fdot2_f32_bf16(g2[p], u2[p], acc, false);
-                    v0[j] = (__bf16)acc;
+                    ovec u8 = *reinterpret_cast<const ovec*>(
+                        u_lds + ((size_t)c * 64 + e) * LP);
+                    v0[j] = (__bf16)dot_ovec<LP>(g8, u8);
                 }
                 *reinterpret_cast<bf16x8*>(reinterpret_cast<char*>(dr_lds)
                     + e * 512 + (((n8 ^ (e & 15)) << 4))) = *reinterpret_cast<bf16x8*>(v0);
@@ -184,26 +181,82 @@ pairconv_bwd_dh_kernel(const __bf16* __restrict__ Gt,  // (mo, O, E) bf16
 }
 
 // ---------------------------------------------------------------------------
+// B2 pieces shared by the dw kernel and its O=1 form: the H^T chunk load, the
+// MFMA step over one 32-edge chunk and the dW tile write.
+// ---------------------------------------------------------------------------
+// spelled out, not load_edges8: with the helper the compiler schedules dw
+// differently and it measured slower (+1.3 % at O=5; profiles/pairconv_prune.md)
+__device__ __forceinline__ bf16x8 dw_load_h(const __bf16* __restrict__ Ht, int E,
+                                            int e0, int tid) {
+    int k = tid >> 2, eu = (tid & 3) * 8;
+    const __bf16* src = Ht + (size_t)k * E + e0 + eu;
+    bf16x8 h(0);
+    if (e0 + eu + 8 <= E) h = *reinterpret_cast<const bf16x8*>(src);
+    else { for (int j = 0; j < 8; ++j) h[j] = (e0 + eu + j < E) ? src[j] : (__bf16)0.f; }
+    return h;
+}
+
+// dW_tile += dR^T(128n x 32e) @ H(32e x 128k); wave (wn, wk) owns 32 n x 64 k
+__device__ __forceinline__ void dw_mfma_chunk(f32x4 (&acc)[2][4], const __bf16* dr_lds,
+                                              const __bf16* h_lds, int wn, int wk,
+                                              int l15, int l4) {
+#pragma unroll
+    for (int nf = 0; nf < 2; ++nf) {
+        bf16x8 a = *reinterpret_cast<const bf16x8*>(
+            dr_lds + (size_t)(wn * 32 + nf * 16 + l15) * 32 + l4 * 8);
+#pragma unroll
+        for (int kf = 0; kf < 4; ++kf) {
+            bf16x8 b = *reinterpret_cast<const bf16x8*>(
+                h_lds + (size_t)(wk * 64 + kf * 16 + l15) * 32 + l4 * 8);
+            acc[nf][kf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc[nf][kf], 0, 0, 0);
+        }
+    }
+}
+
+// D rows = n ((l4*4+reg within frag)), cols = k (l15)
+__device__ __forceinline__ void dw_write_tile(float* __restrict__ dW, const f32x4 (&acc)[2][4],
+                                              int mb, int cb, int miF, int wn, int wk,
+                                              int l15, int l4) {
+    const size_t nbase = (size_t)(mb * 4) * miF + cb * 32;
+#pragma unroll
+    for (int nf = 0; nf < 2; ++nf)
+#pragma unroll
+        for (int kf = 0; kf < 4; ++kf)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                int ntile = wn * 32 + nf * 16 + l4 * 4 + reg;
+                int m = ntile >> 5, c = ntile & 31;
+                int k = wk * 64 + kf * 16 + l15;
+                dW[(nbase + (size_t)m * miF + c) * KDIM + k] = acc[nf][kf][reg];
+            }
+}
+
+// ---------------------------------------------------------------------------
 // B2: dW[n,k] = sum_e dR[e,n] H[e,k];  db[n] = sum_e dR[e,n]
 // block: n-tile 128 (4 mo x 32 urow) x 128 k, loops e in chunks of 32.
 // Ht is H transposed: (128, E) bf16.
+//
+// dR^T build: thread (c = tid >> 4, e-pair = tid & 15) keeps its two u
+// vectors u[c][e], u[c][e+1] in the T14 staging registers — u never goes
+// through LDS, each vector is loaded once — and contracts them with the four
+// g[m][e], g[m][e+1] pairs of the tile by v_dot2_f32_bf16: 8 dR entries per
+// thread, stored as four 4-byte e-pairs into the [128 n][32 e] MFMA image
+// (a wave's stores cover 4 whole 64 B rows: conflict-free). Only the
+// 4 x 32 g vectors and the H^T tile are staged in LDS.
 // ---------------------------------------------------------------------------
 template <int O>
 __global__ void __launch_bounds__(NT)
-pairconv_bwd_dw_kernel(const __bf16* __restrict__ Gt,  // (mo, O, E)
-                       const __bf16* __restrict__ Ut,  // (miF, O, E)
+pairconv_bwd_dw_kernel(const __bf16* __restrict__ Gt,  // (mo, E, OP)
+                       const __bf16* __restrict__ Ut,  // (miF, E, OP)
                        const __bf16* __restrict__ Ht,  // (128, E)
                        float* __restrict__ dW,         // (mo*miF, 128) f32
                        int E, int mo, int miF) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    // NOTE: dw keeps the e-pair packed-fma dR build — the o-padded dot2
-    // layout (as in dh) was tried and measured SLOWER here (234 -> 187
-    // TF/s): dw stages per 32-EDGE chunk, so the scatter commit the padded
-    // layout needs runs every chunk and dominates.
+    constexpr int OP = opad_of(O);
+    typedef typename OVec<OP>::type ovec;
     __bf16* dr_lds = reinterpret_cast<__bf16*>(smem);                  // [128n][32e] 8 KiB
     __bf16* h_lds = reinterpret_cast<__bf16*>(smem + 8192);            // [128k][32e] 8 KiB
-    __bf16* u_lds = reinterpret_cast<__bf16*>(smem + 16384);           // [32][O][32]
-    __bf16* g_lds = reinterpret_cast<__bf16*>(smem + 16384 + 32 * O * 32 * 2); // [4][O][32]
+    __bf16* g_lds = reinterpret_cast<__bf16*>(smem + 16384);           // [4][32][OP]
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -212,9 +265,10 @@ pairconv_bwd_dw_kernel(const __bf16* __restrict__ Gt,  // (mo, O, E)
     const int l4 = lane >> 4;
     const int wn = wid >> 1;          // 0..3: n-group of 32
     const int wk = wid & 1;           // 0..1: k-group of 64
-    // n-tile: blockIdx.x over N/128; tile covers mo-block of 4, urow-chunk of 32
     const int mb = blockIdx.x / (miF / 32);     // mo-block (4 mo each)
     const int cb = blockIdx.x % (miF / 32);     // urow chunk
+    const int uc = tid >> 4;          // 0..31: this thread's urow in the chunk
+    const int ue = (tid & 15) * 2;    // its e-pair in the 32-edge chunk
 
     f32x4 acc[2][4];                  // wave: 32 n x 64 k
 #pragma unroll
@@ -225,63 +279,103 @@ pairconv_bwd_dw_kernel(const __bf16* __restrict__ Gt,  // (mo, O, E)
     // T14 register-staged pipeline: chunk ec+1's global loads are issued
     // right after chunk ec's LDS image is written, so HBM/L2 latency hides
     // under the dR + MFMA phase instead of serializing each chunk.
-    constexpr int UU = (32 * O * 32 / 8 + NT - 1) / NT;   // u 16B units/thread
-    constexpr int GU = 1;                                  // g units/thread
-    bf16x8 u_reg[UU], g_reg[GU], h_reg;
+    ovec u_reg[2], g_reg;
+    bf16x8 h_reg;
     const int nec = (E + 31) / 32;
 
-    // The edge-guarded loads here and in du are spelled out, not
-    // load_edges8: with the helper the compiler schedules these two kernels
-    // differently and they measured slower (dw +1.3 % at O=5, du +4.6 % /
-    // +6 %; profiles/pairconv_prune.md). fwd and dh are indifferent to it.
     auto load_chunk = [&](int ec) {
         const int e0 = ec * 32;
-#pragma unroll
-        for (int t = 0; t < UU; ++t) {
-            int i = tid + t * NT;
-            u_reg[t] = bf16x8(0);
-            if (i < (32 * O * 32) / 8) {
-                int ro = i >> 2, eu = (i & 3) * 8;
-                const __bf16* src = Ut + ((size_t)(cb * 32 + ro / O) * O + (ro % O)) * E + e0 + eu;
-                if (e0 + eu + 8 <= E) u_reg[t] = *reinterpret_cast<const bf16x8*>(src);
-                else { for (int j = 0; j < 8; ++j) u_reg[t][j] = (e0 + eu + j < E) ? src[j] : (__bf16)0.f; }
-            }
-        }
-        {
-            int i = tid;
-            g_reg[0] = bf16x8(0);
-            if (i < (4 * O * 32) / 8) {
-                int ro = i >> 2, eu = (i & 3) * 8;
-                const __bf16* src = Gt + ((size_t)(mb * 4 + ro / O) * O + (ro % O)) * E + e0 + eu;
-                if (e0 + eu + 8 <= E) g_reg[0] = *reinterpret_cast<const bf16x8*>(src);
-                else { for (int j = 0; j < 8; ++j) g_reg[0][j] = (e0 + eu + j < E) ? src[j] : (__bf16)0.f; }
-            }
-        }
-        {
-            int k = tid >> 2, eu = (tid & 3) * 8;
-            const __bf16* src = Ht + (size_t)k * E + e0 + eu;
-            h_reg = bf16x8(0);
-            if (e0 + eu + 8 <= E) h_reg = *reinterpret_cast<const bf16x8*>(src);
-            else { for (int j = 0; j < 8; ++j) h_reg[j] = (e0 + eu + j < E) ? src[j] : (__bf16)0.f; }
-        }
+        u_reg[0] = load_ovec<OP>(Ut, (size_t)(cb * 32 + uc), e0 + ue, E);
+        u_reg[1] = load_ovec<OP>(Ut, (size_t)(cb * 32 + uc), e0 + ue + 1, E);
+        if (tid < 4 * 32)
+            g_reg = load_ovec<OP>(Gt, (size_t)(mb * 4 + (tid >> 5)), e0 + (tid & 31), E);
+        h_reg = dw_load_h(Ht, E, e0, tid);
     };
 
     load_chunk(0);
     for (int ec = 0; ec < nec; ++ec) {
         __syncthreads();   // previous MFMA done reading the LDS images
-        // write the staged registers for chunk ec
+        const ovec u0 = u_reg[0], u1 = u_reg[1];
+        if (tid < 4 * 32)
+            *reinterpret_cast<ovec*>(g_lds + (size_t)tid * OP) = g_reg;
+        {
+            int k = tid >> 2, eu = (tid & 3) * 8;
+            *reinterpret_cast<bf16x8*>(h_lds + (size_t)k * 32 + eu) = h_reg;
+        }
+        if (ec + 1 < nec) load_chunk(ec + 1);   // issue next loads early
+        __syncthreads();
+        // dR^T tile [128n][32e]: this thread's (c, e-pair) against 4 mo
 #pragma unroll
-        for (int t = 0; t < UU; ++t) {
-            int i = tid + t * NT;
-            if (i < (32 * O * 32) / 8) {
-                int ro = i >> 2, eu = (i & 3) * 8;
-                *reinterpret_cast<bf16x8*>(u_lds + (size_t)ro * 32 + eu) = u_reg[t];
-            }
+        for (int m = 0; m < 4; ++m) {
+            ovec g0 = *reinterpret_cast<const ovec*>(g_lds + (size_t)(m * 32 + ue) * OP);
+            ovec g1 = *reinterpret_cast<const ovec*>(g_lds + (size_t)(m * 32 + ue + 1) * OP);
+            *reinterpret_cast<bf16x2*>(dr_lds + (size_t)(m * 32 + uc) * 32 + ue) =
+                bf16x2{(__bf16)dot_ovec<OP>(g0, u0), (__bf16)dot_ovec<OP>(g1, u1)};
         }
-        if (tid < (4 * O * 32) / 8) {
-            int ro = tid >> 2, eu = (tid & 3) * 8;
-            *reinterpret_cast<bf16x8*>(g_lds + (size_t)ro * 32 + eu) = g_reg[0];
-        }
+        __syncthreads();
+        dw_mfma_chunk(acc, dr_lds, h_lds, wn, wk, l15, l4);
+    }
+    __syncthreads();
+    dw_write_tile(dW, acc, mb, cb, miF, wn, wk, l15, l4);
+}
+
+// ---------------------------------------------------------------------------
+// B2 at O=1: G and U are plain [row][E] (the padded layout with OP=1), there
+// is no o to contract, and a dR entry is one product. The tile, the staging
+// pipeline and the MFMA step are those of the kernel above; dR^T is built
+// from LDS images of the g and u rows, as e-pairs.
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(NT)
+pairconv_bwd_dw_o1_kernel(const __bf16* __restrict__ Gt,  // (mo, E)
+                          const __bf16* __restrict__ Ut,  // (miF, E)
+                          const __bf16* __restrict__ Ht,  // (128, E)
+                          float* __restrict__ dW,         // (mo*miF, 128) f32
+                          int E, int mo, int miF) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __bf16* dr_lds = reinterpret_cast<__bf16*>(smem);                  // [128n][32e] 8 KiB
+    __bf16* h_lds = reinterpret_cast<__bf16*>(smem + 8192);            // [128k][32e] 8 KiB
+    __bf16* u_lds = reinterpret_cast<__bf16*>(smem + 16384);           // [32][32]
+    __bf16* g_lds = reinterpret_cast<__bf16*>(smem + 16384 + 32 * 32 * 2); // [4][32]
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wid = tid >> 6;
+    const int l15 = lane & 15;
+    const int l4 = lane >> 4;
+    const int wn = wid >> 1;          // 0..3: n-group of 32
+    const int wk = wid & 1;           // 0..1: k-group of 64
+    const int mb = blockIdx.x / (miF / 32);     // mo-block (4 mo each)
+    const int cb = blockIdx.x % (miF / 32);     // urow chunk
+
+    f32x4 acc[2][4];                  // wave: 32 n x 64 k
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = {0.f, 0.f, 0.f, 0.f};
+
+    // one 8-edge unit of a row: threads 0..127 own the u chunk, 0..15 the g tile
+    auto load_row8 = [&](const __bf16* __restrict__ T, int row0, int e0) {
+        bf16x8 v(0);
+        int ro = tid >> 2, eu = (tid & 3) * 8;
+        const __bf16* src = T + (size_t)(row0 + ro) * E + e0 + eu;
+        if (e0 + eu + 8 <= E) v = *reinterpret_cast<const bf16x8*>(src);
+        else { for (int j = 0; j < 8; ++j) v[j] = (e0 + eu + j < E) ? src[j] : (__bf16)0.f; }
+        return v;
+    };
+    bf16x8 u_reg(0), g_reg(0), h_reg;
+    const int nec = (E + 31) / 32;
+    auto load_chunk = [&](int ec) {
+        const int e0 = ec * 32;
+        if (tid < 128) u_reg = load_row8(Ut, cb * 32, e0);
+        if (tid < 16) g_reg = load_row8(Gt, mb * 4, e0);
+        h_reg = dw_load_h(Ht, E, e0, tid);
+    };
+
+    load_chunk(0);
+    for (int ec = 0; ec < nec; ++ec) {
+        __syncthreads();   // previous MFMA done reading the LDS images
+        if (tid < 128) *reinterpret_cast<bf16x8*>(u_lds + (size_t)tid * 8) = u_reg;
+        if (tid < 16) *reinterpret_cast<bf16x8*>(g_lds + (size_t)tid * 8) = g_reg;
         {
             int k = tid >> 2, eu = (tid & 3) * 8;
             *reinterpret_cast<bf16x8*>(h_lds + (size_t)k * 32 + eu) = h_reg;
@@ -292,51 +386,22 @@ pairconv_bwd_dw_kernel(const __bf16* __restrict__ Gt,  // (mo, O, E)
         for (int i = tid; i < (128 * 32) / 2; i += NT) {
             int e = (i & 15) * 2, n = i >> 4;
             int m = n >> 5, c = n & 31;
-            f32x2 acc2 = {0.f, 0.f};
-#pragma unroll
-            for (int o = 0; o < O; ++o) {
-                f32x2 gv = b2f2(*reinterpret_cast<const bf16x2*>(g_lds + (m * O + o) * 32 + e));
-                f32x2 uv = b2f2(*reinterpret_cast<const bf16x2*>(u_lds + (c * O + o) * 32 + e));
-                acc2[0] = fmaf(gv[0], uv[0], acc2[0]);
-                acc2[1] = fmaf(gv[1], uv[1], acc2[1]);
-            }
+            f32x2 gv = b2f2(*reinterpret_cast<const bf16x2*>(g_lds + m * 32 + e));
+            f32x2 uv = b2f2(*reinterpret_cast<const bf16x2*>(u_lds + c * 32 + e));
             *reinterpret_cast<bf16x2*>(dr_lds + (size_t)n * 32 + e) =
-                bf16x2{(__bf16)acc2[0], (__bf16)acc2[1]};
+                bf16x2{(__bf16)fmaf(gv[0], uv[0], 0.f), (__bf16)fmaf(gv[1], uv[1], 0.f)};
         }
         __syncthreads();
-        // MFMA: dW_tile += dR^T(128n x 32e) @ H(32e x 128k)
-#pragma unroll
-        for (int nf = 0; nf < 2; ++nf) {
-            bf16x8 a = *reinterpret_cast<const bf16x8*>(
-                dr_lds + (size_t)(wn * 32 + nf * 16 + l15) * 32 + l4 * 8);
-#pragma unroll
-            for (int kf = 0; kf < 4; ++kf) {
-                bf16x8 b = *reinterpret_cast<const bf16x8*>(
-                    h_lds + (size_t)(wk * 64 + kf * 16 + l15) * 32 + l4 * 8);
-                acc[nf][kf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc[nf][kf], 0, 0, 0);
-            }
-        }
+        dw_mfma_chunk(acc, dr_lds, h_lds, wn, wk, l15, l4);
     }
     __syncthreads();
-    // write dW: D rows = n ((l4*4+reg within frag)), cols = k (l15)
-    const size_t nbase = (size_t)(mb * 4) * miF + cb * 32;
-#pragma unroll
-    for (int nf = 0; nf < 2; ++nf) {
-#pragma unroll
-        for (int kf = 0; kf < 4; ++kf) {
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                int ntile = wn * 32 + nf * 16 + l4 * 4 + reg;
-                int m = ntile >> 5, c = ntile & 31;
-                int k = wk * 64 + kf * 16 + l15;
-                dW[(nbase + (size_t)m * miF + c) * KDIM + k] = acc[nf][kf][reg];
-            }
-        }
-    }
+    dw_write_tile(dW, acc, mb, cb, miF, wn, wk, l15, l4);
 }
 
 // ---------------------------------------------------------------------------
-// B3: du[c,o,e] = sum_mo R[e,(mo,c)] g[e,mo,o],  R = H @ W^T + bias
+// B3: du[c,e,o] = sum_mo R[e,(mo,c)] g[mo,e,o],  R = H @ W^T + bias
+// G is read as (mo, E, OP) vectors and dU written as (miF, E, OP) vectors;
+// inside, the tiles keep e on the lanes.
 // block: 64 e x 32 urow, loops mo in blocks of 8; the R tile is recomputed by
 // the forward's MFMA loop (mfma_rtile), bounced through LDS, contracted vs g.
 // No W prefetch here: the contraction phase holds more live state than the
@@ -348,12 +413,20 @@ __global__ void __launch_bounds__(NT, 4)   // cap VGPR<=128: 2 blocks/CU
 pairconv_bwd_du_kernel(const __bf16* __restrict__ H,   // (E,128)
                        const __bf16* __restrict__ P,   // packed W as forward
                        const float* __restrict__ bias, // (mo*miF,)
-                       const __bf16* __restrict__ Gt,  // (mo,O,E)
-                       float* __restrict__ dU,         // (miF, O, E) f32
+                       const __bf16* __restrict__ Gt,  // (mo, E, OP)
+                       float* __restrict__ dU,         // (miF, E, OP) f32, pads written 0
                        int E, int mo, int miF, int nmemb, int coh) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __bf16* h_lds = reinterpret_cast<__bf16*>(smem);                   // [64][128] swizzled 16K
     __bf16* r_lds = reinterpret_cast<__bf16*>(smem + 16384);           // [256n][64e] 32K
+    // g and du_acc stay [row][o][e] in LDS, e on the lanes: the contraction
+    // reads scalars that load straight into the high half of a register, so
+    // it converts nothing. Reading g as [m][e][OP] vectors there was tried
+    // two ways and lost (unpacking the vector, +10 % at O=7; per-element
+    // dot2 against (R, 0), +9 % at O=5; profiles/opad_layout.md). The g
+    // vectors are split by the commit, du_acc is gathered by the final write.
+    constexpr int OP = opad_of(O);
+    typedef typename OVec<OP>::type ovec;
     __bf16* g_lds = reinterpret_cast<__bf16*>(smem + 49152);           // [8][O][64]
     float* du_acc = reinterpret_cast<float*>(smem + 49152 + ((8 * O * 64 * 2 + 15) & ~15)); // [32][O][64]
     float* bias_lds = reinterpret_cast<float*>(
@@ -375,21 +448,34 @@ pairconv_bwd_du_kernel(const __bf16* __restrict__ H,   // (E,128)
     for (int i = tid; i < 32 * O * 64; i += NT) du_acc[i] = 0.f;
 
     // T14 register staging: the next mo-block's g tile + bias chunk load
-    // while the current block's MFMA + contraction run (g tile fits one
-    // 16B unit per thread for O <= 7).
-    constexpr int GTOT = (8 * O * 64) / 8;   // g tile in 16B units (<= NT)
-    bf16x8 g_reg;
+    // while the current block's MFMA + contraction run (the g tile is one
+    // (m, e) vector per thread; at O=1, 8 edges of one m for 64 threads).
+    // The g load is a bare predicated load into a register zeroed once (a
+    // thread's edge is in or out of range for the whole kernel).
+    // OPEN: with the contraction identical to the e-contiguous kernel's and
+    // dU bit-equal to it, du still measures 4-10 % slower than that kernel
+    // ((3,3) 16.39 vs 15.58 ms, (2,2) 11.22 vs 10.16, (1,1) 3.50 vs 3.36);
+    // this spelling, load_ovec and a coalesced output store all measure
+    // the same. The cause is not found (profiles/opad_layout.md).
+    ovec g_reg(0);
     float bias_reg;
+    const bool g_in = e0 + lane < E;
     auto load_gb = [&](int mb) {
-        if (tid < GTOT) {   // spelled out on purpose: see the note in dw
-            int ro = tid >> 3, eu = (tid & 7) * 8;
-            const __bf16* src = Gt + ((size_t)(mb * 8 + ro / O) * O + (ro % O)) * E + e0 + eu;
-            if (e0 + eu + 8 <= E) g_reg = *reinterpret_cast<const bf16x8*>(src);
-            else {
-                bf16x8 v(0);
-                for (int j = 0; j < 8; ++j) if (e0 + eu + j < E) v[j] = src[j];
-                g_reg = v;
+        if constexpr (O == 1) {
+            if (tid < 64) {   // spelled out on purpose: see dw_load_h
+                int ro = tid >> 3, eu = (tid & 7) * 8;
+                const __bf16* src = Gt + (size_t)(mb * 8 + ro) * E + e0 + eu;
+                if (e0 + eu + 8 <= E) g_reg = *reinterpret_cast<const bf16x8*>(src);
+                else {
+                    bf16x8 v(0);
+                    for (int j = 0; j < 8; ++j) if (e0 + eu + j < E) v[j] = src[j];
+                    g_reg = v;
+                }
             }
+        } else {
+            if (g_in)
+                g_reg = *reinterpret_cast<const ovec*>(
+                    Gt + ((size_t)(mb * 8 + (tid >> 6)) * E + e0 + lane) * OP);
         }
         if (tid < 256) {
             int m = tid >> 5, c = tid & 31;
@@ -402,10 +488,13 @@ pairconv_bwd_du_kernel(const __bf16* __restrict__ H,   // (E,128)
     __syncthreads();
 
     for (int mb = 0; mb < nmo; ++mb) {
-        // commit the staged g tile [8][O][64] + bias chunk [256]
-        if (tid < GTOT) {
-            int ro = tid >> 3, eu = (tid & 7) * 8;
-            *reinterpret_cast<bf16x8*>(g_lds + (size_t)ro * 64 + eu) = g_reg;
+        // commit the staged g tile as [8][O][64] + bias chunk [256]
+        if constexpr (O == 1) {
+            if (tid < 64) *reinterpret_cast<bf16x8*>(g_lds + (size_t)tid * 8) = g_reg;
+        } else {
+#pragma unroll
+            for (int o = 0; o < O; ++o)
+                g_lds[((tid >> 6) * O + o) * 64 + lane] = g_reg[o];
         }
         if (tid < 256) bias_lds[tid] = bias_reg;
         if (mb + 1 < nmo) load_gb(mb + 1);   // issue next block's loads early
@@ -445,22 +534,50 @@ pairconv_bwd_du_kernel(const __bf16* __restrict__ H,   // (E,128)
         }
         __syncthreads();
     }
-    // write du chunk
-    for (int i = tid; i < 32 * O * 64; i += NT) {
-        int e = i & 63, ro = i >> 6;  // c*O+o
-        if (e0 + e < E)
-            dU[((size_t)(uc0 + ro / O) * O + (ro % O)) * E + e0 + e] = du_acc[i];
+    // write the du chunk as (c, e) vectors of OP floats, pads zero: 16 B
+    // units, consecutive lanes on consecutive units, so a wave's store
+    // instruction covers 1 KiB of whole lines
+    if constexpr (O == 1) {
+        for (int i = tid; i < 32 * 64; i += NT) {
+            int e = i & 63, c = i >> 6;
+            if (e0 + e < E) dU[(size_t)(uc0 + c) * E + e0 + e] = du_acc[i];
+        }
+    } else {
+        constexpr int Q = OP / 4;                 // units per (c, e)
+        for (int u = tid; u < 32 * 64 * Q; u += NT) {
+            int q = u % Q, cell = u / Q;
+            int e = cell & 63, c = cell >> 6;
+            if (e0 + e < E) {
+                f32x4 v;
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    v[j] = (q * 4 + j < O) ? du_acc[(c * O + q * 4 + j) * 64 + e] : 0.f;
+                *reinterpret_cast<f32x4*>(
+                    dU + ((size_t)(uc0 + c) * E + e0 + e) * OP + q * 4) = v;
+            }
+        }
     }
 }
 
 // ---------------------------------------------------------------------------
-// launchers
+// launchers. G is (mo, E, OP), U (miF, E, OP), dU (miF, E, OP), OP = opad_of(O)
 // ---------------------------------------------------------------------------
+static void check_opad(const torch::Tensor& T, const char* name, int64_t rows,
+                       int E, int O, c10::ScalarType dt) {
+    TORCH_CHECK(O == 1 || O == 3 || O == 5 || O == 7, "unsupported O ", O);
+    TORCH_CHECK(T.is_cuda() && T.is_contiguous() && T.dtype() == dt && T.dim() == 3 &&
+                T.size(0) == rows && T.size(1) == E && T.size(2) == opad_of(O),
+                name, " must be (rows, E, OP(O)) contiguous");
+}
+
 void pairconv_bwd_dh(torch::Tensor Gt, torch::Tensor Ut, torch::Tensor Wt,
-                     torch::Tensor dH, int64_t mo_) {
-    int E = dH.size(0), mo = (int)mo_, miF = Ut.size(0), O = Ut.size(1);
-    TORCH_CHECK(Gt.is_contiguous() && Ut.is_contiguous() && Wt.is_contiguous() && dH.is_contiguous());
+                     torch::Tensor dH, int64_t mo_, int64_t O_) {
+    int E = dH.size(0), mo = (int)mo_, miF = Ut.size(0), O = (int)O_;
+    check_opad(Gt, "G", mo, E, O, torch::kBFloat16);
+    check_opad(Ut, "U", miF, E, O, torch::kBFloat16);
+    TORCH_CHECK(Wt.is_contiguous() && dH.is_contiguous() && dH.dtype() == torch::kFloat32);
     TORCH_CHECK(Wt.numel() == (int64_t)mo * miF * KDIM, "expect packed W (P1)");
+    TORCH_CHECK(mo % 8 == 0 && miF % 32 == 0 && dH.size(1) == KDIM);
     auto stream = at::cuda::getCurrentHIPStream();
     int eblk = (E + 63) / 64;
     int nmo = mo / 8;
@@ -471,7 +588,8 @@ void pairconv_bwd_dh(torch::Tensor Gt, torch::Tensor Ut, torch::Tensor Wt,
     int panels = ((eblk + PE - 1) / PE) * ((nsplit + PS - 1) / PS);
     dim3 grid((long)panels * PS * PE);
     DISPATCH_O(O, {
-        size_t lds = 32768 + 32768 + 8192;   // dr | u[32][64][8] | g[8][64][8]
+        constexpr int LP = (kO == 1) ? 8 : opad_of(kO);
+        size_t lds = 32768 + (size_t)(32 + 8) * 64 * LP * 2;   // dr | u[32][64][LP] | g[8][64][LP]
         hipLaunchKernelGGL(HIP_KERNEL_NAME(pairconv_bwd_dh_kernel<kO>), grid, dim3(NT), lds, stream,
                            reinterpret_cast<const __bf16*>(Gt.data_ptr()),
                            reinterpret_cast<const __bf16*>(Ut.data_ptr()),
@@ -482,33 +600,51 @@ void pairconv_bwd_dh(torch::Tensor Gt, torch::Tensor Ut, torch::Tensor Wt,
     TORCH_CHECK(err == hipSuccess, "bwd_dh: ", hipGetErrorString(err));
 }
 
+template <int O>
+static void launch_dw(dim3 grid, hipStream_t stream, const __bf16* Gt,
+                      const __bf16* Ut, const __bf16* Ht, float* dW,
+                      int E, int mo, int miF) {
+    if constexpr (O == 1) {
+        size_t lds = 16384 + (size_t)32 * 32 * 2 + (size_t)4 * 32 * 2;
+        hipLaunchKernelGGL(pairconv_bwd_dw_o1_kernel, grid,
+                           dim3(NT), lds, stream, Gt, Ut, Ht, dW, E, mo, miF);
+    } else {
+        size_t lds = 16384 + (size_t)4 * 32 * opad_of(O) * 2;   // dr | h | g[4][32][OP]
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(pairconv_bwd_dw_kernel<O>), grid,
+                           dim3(NT), lds, stream, Gt, Ut, Ht, dW, E, mo, miF);
+    }
+}
+
 void pairconv_bwd_dw(torch::Tensor Gt, torch::Tensor Ut, torch::Tensor Ht,
-                     torch::Tensor dW, int64_t mo_) {
-    int E = Ht.size(1), mo = (int)mo_, miF = Ut.size(0), O = Ut.size(1);
-    TORCH_CHECK(Gt.is_contiguous() && Ut.is_contiguous() && Ht.is_contiguous() &&
-                dW.is_contiguous());
+                     torch::Tensor dW, int64_t mo_, int64_t O_) {
+    int E = Ht.size(1), mo = (int)mo_, miF = Ut.size(0), O = (int)O_;
+    check_opad(Gt, "G", mo, E, O, torch::kBFloat16);
+    check_opad(Ut, "U", miF, E, O, torch::kBFloat16);
+    TORCH_CHECK(Ht.is_contiguous() && Ht.dtype() == torch::kBFloat16 && Ht.size(0) == KDIM);
+    TORCH_CHECK(dW.is_contiguous() && dW.dtype() == torch::kFloat32 &&
+                dW.numel() == (int64_t)mo * miF * KDIM);
     TORCH_CHECK(mo % 4 == 0 && miF % 32 == 0);
     auto stream = at::cuda::getCurrentHIPStream();
     dim3 grid((mo / 4) * (miF / 32));
-    DISPATCH_O(O, {
-        size_t lds = 16384 + (size_t)32 * kO * 32 * 2 + (size_t)4 * kO * 32 * 2;
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(pairconv_bwd_dw_kernel<kO>), grid, dim3(NT), lds, stream,
-                           reinterpret_cast<const __bf16*>(Gt.data_ptr()),
-                           reinterpret_cast<const __bf16*>(Ut.data_ptr()),
-                           reinterpret_cast<const __bf16*>(Ht.data_ptr()),
-                           dW.data_ptr<float>(), E, mo, miF);
-    });
+    DISPATCH_O(O, launch_dw<kO>(grid, stream,
+                                reinterpret_cast<const __bf16*>(Gt.data_ptr()),
+                                reinterpret_cast<const __bf16*>(Ut.data_ptr()),
+                                reinterpret_cast<const __bf16*>(Ht.data_ptr()),
+                                dW.data_ptr<float>(), E, mo, miF));
     hipError_t err = hipGetLastError();
     TORCH_CHECK(err == hipSuccess, "bwd_dw: ", hipGetErrorString(err));
 }
 
 void pairconv_bwd_du(torch::Tensor H, torch::Tensor W, torch::Tensor bias,
-                     torch::Tensor Gt, torch::Tensor dU, int64_t mo_) {
-    int E = H.size(0), mo = (int)mo_, miF = dU.size(0), O = dU.size(1);
-    TORCH_CHECK(H.is_contiguous() && W.is_contiguous() && Gt.is_contiguous() &&
-                bias.is_contiguous() && dU.is_contiguous());
+                     torch::Tensor Gt, torch::Tensor dU, int64_t mo_, int64_t O_) {
+    int E = H.size(0), mo = (int)mo_, miF = dU.size(0), O = (int)O_;
+    check_opad(Gt, "G", mo, E, O, torch::kBFloat16);
+    check_opad(dU, "dU", miF, E, O, torch::kFloat32);
+    TORCH_CHECK(H.is_contiguous() && W.is_contiguous() && bias.is_contiguous());
+    TORCH_CHECK(H.dtype() == torch::kBFloat16 && H.size(1) == KDIM);
     TORCH_CHECK(W.numel() == (int64_t)mo * miF * KDIM, "expect packed W (P)");
-    TORCH_CHECK(bias.dtype() == torch::kFloat32);
+    TORCH_CHECK(bias.dtype() == torch::kFloat32 && bias.numel() == (int64_t)mo * miF);
+    TORCH_CHECK(mo % 8 == 0 && miF % 32 == 0);
     auto stream = at::cuda::getCurrentHIPStream();
     int nmemb = (E + 63) / 64;
     int ncb = miF / 32;

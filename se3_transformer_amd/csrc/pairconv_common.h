@@ -8,12 +8,51 @@
 #include <ATen/hip/HIPContext.h>
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
+// 16 B load from an address that is only 8 B aligned (two OP=4 vectors)
+typedef bf16x8 bf16x8_a8 __attribute__((aligned(8)));
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 
 #define KDIM 128   // radial hidden width = GEMM K
 #define NT 512     // threads per block (8 waves) in all four kernels
+
+// Padded o width OP(O) of the edge-major tensors U (miF, E, OP) bf16,
+// G (mo, E, OP) bf16 and dU (miF, E, OP) f32: all o of one (row, edge) are
+// one aligned vector, and the pad lanes o in [O, OP) are exactly zero, so a
+// consumer contracts whole vectors. The one definition; Python reads it
+// through pairconv_opad().
+__host__ __device__ constexpr int opad_of(int O) {
+    return O == 1 ? 1 : (O <= 3 ? 4 : 8);
+}
+
+// The (row, edge) vector of an o-padded tensor: 16 B at OP=8, 8 B at OP=4.
+// O=1 has no vector form (its layout is the plain [row][E] the kernels
+// always used); OVec<1> only keeps the O=1 instantiations well-formed.
+template <int OP> struct OVec { typedef bf16x8 type; };
+template <> struct OVec<4> { typedef bf16x4 type; };
+
+template <int OP>
+__device__ __forceinline__ typename OVec<OP>::type
+load_ovec(const __bf16* __restrict__ T, size_t row, int e, int E) {
+    typedef typename OVec<OP>::type V;
+    if (e < E) return *reinterpret_cast<const V*>(T + (row * E + e) * OP);
+    return V(0);
+}
+
+// sum_o a[o] b[o] over one padded vector: OP/2 v_dot2_f32_bf16.
+template <int OP>
+__device__ __forceinline__ float dot_ovec(typename OVec<OP>::type a,
+                                          typename OVec<OP>::type b) {
+    const bf16x2* a2 = reinterpret_cast<const bf16x2*>(&a);
+    const bf16x2* b2 = reinterpret_cast<const bf16x2*>(&b);
+    float acc = 0.f;
+#pragma unroll
+    for (int p = 0; p < OP / 2; ++p)
+        acc = __builtin_amdgcn_fdot2_f32_bf16(a2[p], b2[p], acc, false);
+    return acc;
+}
 
 __device__ __forceinline__ float b2f(__bf16 x) { return (float)x; }
 
@@ -24,8 +63,8 @@ __device__ __forceinline__ f32x2 b2f2(bf16x2 v) {
 // 8 consecutive edges e..e+7 of one e-contiguous row (Ut, Gt, Ht rows are
 // E long and in general not 16B aligned): one full vector when the run is
 // inside E, element by element with zero fill across the ragged end.
-// Used by fwd and dh; dw and du keep their own spelling (see the note in
-// pairconv_bwd_dw_kernel).
+// Used by the O=1 instantiations of fwd and dh, whose [row][E] tensors are
+// not o-padded.
 __device__ __forceinline__ bf16x8 load_edges8(const __bf16* __restrict__ row,
                                               int e, int E) {
     const __bf16* src = row + e;
@@ -39,6 +78,7 @@ __device__ __forceinline__ bf16x8 load_edges8(const __bf16* __restrict__ row,
 // Scatter 8 edges of (row, o) into an LDS tile laid out [row][64 e][o PADDED
 // to 8], so the consumer reads all o of one (row, e) as a single 16B vector.
 // The pad lanes o in [O, 8) are zeroed once by the caller and never written.
+// Only the O=1 instantiations of fwd and dh still stage this way.
 __device__ __forceinline__ void commit_opad(__bf16* tile, int row, int eu,
                                             int o, bf16x8 v) {
 #pragma unroll

@@ -1,18 +1,23 @@
 // Basis-feature precontraction ("u build") for the fused pairwise conv:
 //
-//   Ut[(c*F + f), o, e] = sum_i  B[e, o, i, f] * X[e, c, i]
+//   U[(c*F + f), e, o] = sum_i  B[e, o, i, f] * X[e, c, i]
 //
-// This is the `torch.einsum('eoif,eci->cfoe')` in PairwiseConv.apply_fused
+// U is (C*F, E, OP): edge-major with o padded to OP = opad_of(O)
+// (pairconv_common.h), pad lanes written as zeros. dU has the same shape in
+// f32.
+//
+// This is the `torch.einsum('eoif,eci->cfeo')` in PairwiseConv.apply_fused
 // (reference contraction se3_transformer_pytorch.py:336-338 restructured,
 // see models/core.py) — in eager torch it lowers to permute-copies + bmm +
 // an output copy (the largest non-custom slice of the round-1/2 kernel
 // stats). Here: one pass, B staged once per edge tile in LDS (it is re-used
-// by all C channels), output written directly in the e-contiguous layout
-// the pairconv kernels consume.
+// by all C channels), output written directly in the padded layout the
+// pairconv kernels consume: the thread that owns a (row, e) computes all its
+// o and writes the whole vector, pads included.
 //
 // Backward:
-//   dX[e, c, i]    = sum_{f,o} B[e,o,i,f] * dU[(c*F+f), o, e]   (always)
-//   dB[e, o, i, f] = sum_c     X[e,c,i]   * dU[(c*F+f), o, e]   (only when the
+//   dX[e, c, i]    = sum_{f,o} B[e,o,i,f] * dU[(c*F+f), e, o]   (always)
+//   dB[e, o, i, f] = sum_c     X[e,c,i]   * dU[(c*F+f), e, o]   (only when the
 // basis requires grad, i.e. differentiable_coors). dB is a sibling kernel
 // rather than a second output of the dX kernel: the dX kernel's LDS already
 // holds B and a dU tile, and adding the fp32 dB tile would pass 64 KiB for
@@ -21,8 +26,7 @@
 #include <torch/extension.h>
 #include <hip/hip_runtime.h>
 #include <ATen/hip/HIPContext.h>
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+#include "pairconv_common.h"
 
 #define UB_NT 256
 #define UB_E 32          // edges per block (fwd)
@@ -32,11 +36,11 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 
 typedef __attribute__((ext_vector_type(2))) __bf16 ub_bf16x2;
 
-template <typename TX>
+template <typename TX, int OP>
 __global__ void __launch_bounds__(UB_NT)
 ubuild_fwd_kernel(const float* __restrict__ B,   // (E, O, I, F)
                   const TX* __restrict__ X,      // (E, C, I)
-                  __bf16* __restrict__ Ut,       // (C*F, O, E)
+                  __bf16* __restrict__ Ut,       // (C*F, E, OP)
                   int E, int C, int O, int I, int F) {
     // b and x tiles are stored [.., i PADDED to 8] bf16 so each output
     // element is two 16B LDS reads + 4 v_dot2_f32_bf16 over i
@@ -71,26 +75,37 @@ ubuild_fwd_kernel(const float* __restrict__ B,   // (E, O, I, F)
                     ? (float)X[((size_t)(e0 + e) * C + c0 + c) * I + i] : 0.f);
         }
         __syncthreads();
-        // out elements of this chunk: (c 32) x (f F) x (o O) x (e 32), e minor
-        const int nel = UB_C * F * O * UB_E;
+        // out vectors of this chunk: (c 32) x (f F) x (e 32), e minor; the
+        // thread computes all O lanes of its vector and stores it whole
+        const int nel = UB_C * F * UB_E;
         for (int t = tid; t < nel; t += UB_NT) {
             int e = t & (UB_E - 1);
-            int r = t / UB_E;          // ((c*F + f)*O + o)
-            int o = r % O;
-            int cf = r / O;
+            int cf = t / UB_E;         // c*F + f
             int f = cf % F, c = cf / F;
-            bf16x8 bv = *reinterpret_cast<const bf16x8*>(
-                b_lds + ((size_t)e * of + o * F + f) * 8);
             bf16x8 xv = *reinterpret_cast<const bf16x8*>(
                 x_lds + ((size_t)c * UB_E + e) * 8);
-            const ub_bf16x2* b2 = reinterpret_cast<const ub_bf16x2*>(&bv);
             const ub_bf16x2* x2 = reinterpret_cast<const ub_bf16x2*>(&xv);
-            float acc = 0.f;
+            __bf16 v[OP];
 #pragma unroll
-            for (int p = 0; p < 4; ++p)
-                acc = __builtin_amdgcn_fdot2_f32_bf16(b2[p], x2[p], acc, false);
-            if (e0 + e < E)
-                Ut[((size_t)((c0 + c) * F + f) * O + o) * E + e0 + e] = (__bf16)acc;
+            for (int o = 0; o < OP; ++o) {
+                v[o] = (__bf16)0.f;
+                if (o < O) {
+                    bf16x8 bv = *reinterpret_cast<const bf16x8*>(
+                        b_lds + ((size_t)e * of + o * F + f) * 8);
+                    const ub_bf16x2* b2 = reinterpret_cast<const ub_bf16x2*>(&bv);
+                    float acc = 0.f;
+#pragma unroll
+                    for (int p = 0; p < 4; ++p)
+                        acc = __builtin_amdgcn_fdot2_f32_bf16(b2[p], x2[p], acc, false);
+                    v[o] = (__bf16)acc;
+                }
+            }
+            if (e0 + e < E) {
+                __bf16* dst = Ut + (((size_t)(c0 + c) * F + f) * E + e0 + e) * OP;
+                if constexpr (OP == 1) dst[0] = v[0];
+                else *reinterpret_cast<typename OVec<OP>::type*>(dst) =
+                         *reinterpret_cast<typename OVec<OP>::type*>(v);
+            }
         }
     }
 }
@@ -98,7 +113,7 @@ ubuild_fwd_kernel(const float* __restrict__ B,   // (E, O, I, F)
 template <typename TX>
 __global__ void __launch_bounds__(UB_NT)
 ubuild_bwd_dx_kernel(const float* __restrict__ B,   // (E, O, I, F)
-                     const float* __restrict__ dU,  // (C*F, O, E) f32
+                     const float* __restrict__ dU,  // (C*F, E, OP) f32
                      TX* __restrict__ dX,           // (E, C, I)
                      int E, int C, int O, int I, int F) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -109,6 +124,7 @@ ubuild_bwd_dx_kernel(const float* __restrict__ B,   // (E, O, I, F)
     const int e0 = blockIdx.x * UB_EB;
     const int oif = O * I * F;
     const int fo = F * O;
+    const int OP = opad_of(O);
 
     for (int t = tid; t < UB_EB * oif; t += UB_NT) {
         int e = t / oif, r = t % oif;
@@ -117,13 +133,16 @@ ubuild_bwd_dx_kernel(const float* __restrict__ B,   // (E, O, I, F)
 
     for (int c0 = 0; c0 < C; c0 += UB_CB) {
         __syncthreads();
-        for (int t = tid; t < UB_CB * fo * UB_EB; t += UB_NT) {
-            int e = t % UB_EB;
-            int r = t / UB_EB;         // c*F*O + (f*O + o)
-            int c = r / fo, fo_i = r % fo;
-            int f = fo_i / O, o = fo_i % O;
-            g_lds[(c * fo + fo_i) * UB_EB + e] = (e0 + e < E)
-                ? dU[((size_t)((c0 + c) * F + f) * O + o) * E + e0 + e] : 0.f;
+        // dU tile, read in memory order (o minor, pads skipped)
+        for (int t = tid; t < UB_CB * F * UB_EB * OP; t += UB_NT) {
+            int o = t % OP;
+            int r = t / OP;
+            int e = r % UB_EB;
+            int cf = r / UB_EB;        // c*F + f
+            int c = cf / F, f = cf % F;
+            if (o < O)
+                g_lds[(c * fo + f * O + o) * UB_EB + e] = (e0 + e < E)
+                    ? dU[(((size_t)(c0 + c) * F + f) * E + e0 + e) * OP + o] : 0.f;
         }
         __syncthreads();
         // dX elements: (c 8) x (i I) x (e 16), e minor
@@ -154,7 +173,7 @@ ubuild_bwd_dx_kernel(const float* __restrict__ B,   // (E, O, I, F)
 template <typename TX>
 __global__ void __launch_bounds__(UB_NT)
 ubuild_bwd_db_kernel(const TX* __restrict__ X,      // (E, C, I)
-                     const float* __restrict__ dU,  // (C*F, O, E) f32
+                     const float* __restrict__ dU,  // (C*F, E, OP) f32
                      float* __restrict__ dB,        // (E, O, I, F)
                      int E, int C, int O, int I, int F) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -165,6 +184,7 @@ ubuild_bwd_db_kernel(const TX* __restrict__ X,      // (E, C, I)
     const int e0 = blockIdx.x * UB_EB;
     const int oif = O * I * F;
     const int fo = F * O;
+    const int OP = opad_of(O);
     const int nout = UB_EB * oif;
 
     // per-output LDS offsets (channel 0), packed: x offset | g offset << 10
@@ -183,13 +203,15 @@ ubuild_bwd_db_kernel(const TX* __restrict__ X,      // (E, C, I)
 
     for (int c0 = 0; c0 < C; c0 += UB_CB) {
         __syncthreads();
-        for (int t = tid; t < UB_CB * fo * UB_EB; t += UB_NT) {
-            int e = t % UB_EB;
-            int r = t / UB_EB;         // c*F*O + (f*O + o)
-            int c = r / fo, fo_i = r % fo;
-            int f = fo_i / O, o = fo_i % O;
-            g_lds[t] = (e0 + e < E)
-                ? dU[((size_t)((c0 + c) * F + f) * O + o) * E + e0 + e] : 0.f;
+        for (int t = tid; t < UB_CB * F * UB_EB * OP; t += UB_NT) {
+            int o = t % OP;
+            int r = t / OP;
+            int e = r % UB_EB;
+            int cf = r / UB_EB;        // c*F + f
+            int c = cf / F, f = cf % F;
+            if (o < O)
+                g_lds[(c * fo + f * O + o) * UB_EB + e] = (e0 + e < E)
+                    ? dU[(((size_t)(c0 + c) * F + f) * E + e0 + e) * OP + o] : 0.f;
         }
         for (int t = tid; t < UB_CB * I * UB_EB; t += UB_NT) {
             int e = t % UB_EB;
@@ -229,26 +251,36 @@ void ubuild_fwd(torch::Tensor B, torch::Tensor X, torch::Tensor Ut,
                 Ut.dtype() == torch::kBFloat16);
     int E = B.size(0);
     int C = X.size(1);
+    TORCH_CHECK(O == 1 || O == 3 || O == 5 || O == 7, "unsupported O ", O);
+    const int OP = opad_of((int)O);
+    TORCH_CHECK(Ut.dim() == 3 && Ut.size(0) == (int64_t)C * F && Ut.size(1) == E &&
+                Ut.size(2) == OP, "expect U as (C*F, E, OP(O))");
+    TORCH_CHECK(B.numel() == (int64_t)E * O * I * F && X.size(0) == E && X.size(2) == I);
     TORCH_CHECK(C % UB_C == 0, "channels must be a multiple of 32");
     TORCH_CHECK(O * I * F <= 343, "degree pair too large for LDS staging");
     TORCH_CHECK(I <= 8, "I (2*d_in+1) must be <= 8");
     auto stream = at::cuda::getCurrentHIPStream();
     dim3 grid((E + UB_E - 1) / UB_E);
     size_t lds = (size_t)UB_E * O * F * 8 * 2 + (size_t)UB_C * UB_E * 8 * 2;
+#define UB_LAUNCH_FWD(TX, XPTR, OPV)                                          \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(ubuild_fwd_kernel<TX, OPV>), grid,        \
+                       dim3(UB_NT), lds, stream, B.data_ptr<float>(), XPTR,      \
+                       reinterpret_cast<__bf16*>(Ut.data_ptr()),                 \
+                       E, C, (int)O, (int)I, (int)F)
+#define UB_LAUNCH_FWD_OP(TX, XPTR)                                               \
+    do {                                                                         \
+        if (OP == 8) UB_LAUNCH_FWD(TX, XPTR, 8);                                 \
+        else if (OP == 4) UB_LAUNCH_FWD(TX, XPTR, 4);                            \
+        else UB_LAUNCH_FWD(TX, XPTR, 1);                                         \
+    } while (0)
     if (X.dtype() == torch::kFloat32) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(ubuild_fwd_kernel<float>), grid,
-                           dim3(UB_NT), lds, stream, B.data_ptr<float>(),
-                           X.data_ptr<float>(),
-                           reinterpret_cast<__bf16*>(Ut.data_ptr()),
-                           E, C, (int)O, (int)I, (int)F);
+        UB_LAUNCH_FWD_OP(float, X.data_ptr<float>());
     } else {
         TORCH_CHECK(X.dtype() == torch::kBFloat16);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(ubuild_fwd_kernel<__bf16>), grid,
-                           dim3(UB_NT), lds, stream, B.data_ptr<float>(),
-                           reinterpret_cast<const __bf16*>(X.data_ptr()),
-                           reinterpret_cast<__bf16*>(Ut.data_ptr()),
-                           E, C, (int)O, (int)I, (int)F);
+        UB_LAUNCH_FWD_OP(__bf16, reinterpret_cast<const __bf16*>(X.data_ptr()));
     }
+#undef UB_LAUNCH_FWD_OP
+#undef UB_LAUNCH_FWD
     hipError_t err = hipGetLastError();
     TORCH_CHECK(err == hipSuccess, "ubuild_fwd: ", hipGetErrorString(err));
 }
@@ -262,6 +294,9 @@ void ubuild_bwd_dx(torch::Tensor B, torch::Tensor dU, torch::Tensor dX,
     int C = dX.size(1);
     TORCH_CHECK(C % UB_CB == 0, "channels must be a multiple of 8");
     TORCH_CHECK(O * I * F <= 343);
+    TORCH_CHECK(O == 1 || O == 3 || O == 5 || O == 7, "unsupported O ", O);
+    TORCH_CHECK(dU.numel() == (int64_t)C * F * E * opad_of((int)O),
+                "expect dU as (C*F, E, OP(O))");
     auto stream = at::cuda::getCurrentHIPStream();
     dim3 grid((E + UB_EB - 1) / UB_EB);
     size_t lds = (size_t)UB_EB * O * I * F * 4 + (size_t)UB_CB * F * O * UB_EB * 4;
@@ -291,7 +326,9 @@ void ubuild_bwd_db(torch::Tensor X, torch::Tensor dU, torch::Tensor dB,
                 dB.dtype() == torch::kFloat32);
     int E = X.size(0);
     int C = X.size(1);
-    TORCH_CHECK(X.size(2) == I && dU.numel() == (int64_t)C * F * O * E &&
+    TORCH_CHECK(O == 1 || O == 3 || O == 5 || O == 7, "unsupported O ", O);
+    TORCH_CHECK(X.size(2) == I &&
+                dU.numel() == (int64_t)C * F * E * opad_of((int)O) &&
                 dB.numel() == (int64_t)E * O * I * F);
     TORCH_CHECK(C % UB_CB == 0, "channels must be a multiple of 8");
     TORCH_CHECK(O * I * F <= 343);

@@ -275,16 +275,19 @@ class PairwiseConv(nn.Module):
                 and _fused.fused_shapes_ok(mo, mi * F_, O, self.rp.mid_dim)):
             _fused.require_ext()
             h = self.rp.hidden(ef)                           # (E, 128)
-            # u_t[(mi,f), o, e] = sum_i B[e,o,i,f] x[e,mi,i]
+            # u[(mi,f), e, o] = sum_i B[e,o,i,f] x[e,mi,i], written once in
+            # the o-padded layout every pairconv kernel reads
+            w6 = self.rp.net[6]
             if (_fused.ubuild_ok(braw, mi, O, I, F_)
                     and os.environ.get('SE3_EAGER_UBUILD') != '1'):
-                u_t = _fused.ubuild(xg, braw.contiguous(), O, I, F_)
+                u = _fused.ubuild_opad(xg, braw.contiguous(), O, I, F_)
+                out = _fused.fused_pairconv_opad(h, w6.weight, w6.bias, u,
+                                                 mo, O)
             else:
                 u_t = torch.einsum('eoif,eci->cfoe',
                                    braw.to(xg.dtype), xg) \
                     .reshape(mi * F_, O, e_total)
-            w6 = self.rp.net[6]
-            out = _fused.fused_pairconv(h, w6.weight, w6.bias, u_t, mo)
+                out = _fused.fused_pairconv(h, w6.weight, w6.bias, u_t, mo)
             return out.view(*lead, mo, O).to(xg.dtype)
 
         # u: (E, mi*F, O), (mi-major, f-minor) matching R's (mo, mi*F) layout

@@ -22,8 +22,9 @@ _EXT_ERR = None
 # caller probes the module again: a stale build is an error at load, not a
 # reason to run eager.
 _ENTRY_POINTS = (
-    'pairconv_fwd', 'pairconv_bwd_dh', 'pairconv_bwd_dw', 'pairconv_bwd_du',
-    'pack_w_both', 'radial_trunk_fwd', 'radial_trunk_bwd',
+    'pairconv_fwd', 'pairconv_fwd_opad', 'pairconv_opad',
+    'pairconv_bwd_dh', 'pairconv_bwd_dw', 'pairconv_bwd_du',
+    'pack_w_both', 'pack_g', 'radial_trunk_fwd', 'radial_trunk_bwd',
     'ubuild_fwd', 'ubuild_bwd_dx', 'ubuild_bwd_db',
     'sh_basis_fwd', 'sh_basis_bwd', 'knn_graph', 'knn_max_lds_bytes',
     'attn2_fwd', 'attn2_bwd',
@@ -126,24 +127,46 @@ def _pack_w_dh(W16, mo, miF):
     return v.permute(0, 2, 5, 6, 1, 3, 7, 4).contiguous()
 
 
-class _FusedPairConv(torch.autograd.Function):
-    """out[e,mo,o] = sum_{c,h} (H[e,h] W[(mo,c),h] + bias[(mo,c)]) * Ut[c,o,e]
+_OPAD = {}
 
-    H  (E,128) bf16 | W (mo*miF,128) fp32/bf16 param | bias (mo*miF,) fp32
-    Ut (miF,O,E) bf16 | returns (E, mo, O) fp32.
+
+def opad(O: int) -> int:
+    """Padded o width OP(O) of the edge-major tensors U (miF, E, OP),
+    G (mo, E, OP) and dU (miF, E, OP): 7, 5 -> 8; 3 -> 4; 1 -> 1. Defined
+    once, in csrc/pairconv_common.h; read from the extension."""
+    if O not in _OPAD:
+        _OPAD[O] = int(_load_ext().pairconv_opad(O))
+    return _OPAD[O]
+
+
+def _to_opad(Ut, O):
+    """(rows, O, E) -> (rows, E, OP) contiguous with zero pads."""
+    return torch.nn.functional.pad(Ut.permute(0, 2, 1),
+                                   (0, opad(O) - O)).contiguous()
+
+
+class _FusedPairConvOpad(torch.autograd.Function):
+    """out[e,mo,o] = sum_{c,h} (H[e,h] W[(mo,c),h] + bias[(mo,c)]) * U[c,e,o]
+
+    H (E,128) bf16 | W (mo*miF,128) fp32/bf16 param | bias (mo*miF,) fp32
+    U (miF,E,OP) bf16, pad lanes o in [O, OP) exactly zero | returns
+    (E, mo, O) fp32. The gradient of U comes back (miF,E,OP) fp32 with zero
+    pads. The kernels contract whole padded vectors and the two library
+    GEMMs (bias term, db) read U and G as (rows, E*OP) matrices: both rely
+    on the zero pads.
     """
 
     @staticmethod
-    def forward(ctx, H, W, bias, Ut, mo):
+    def forward(ctx, H, W, bias, U, mo, O):
         ext = _load_ext()
         E = H.shape[0]
-        miF, O, _ = Ut.shape
+        miF, _, OP = U.shape
         H16 = H.contiguous().to(torch.bfloat16)
-        Ut16 = Ut.contiguous().to(torch.bfloat16)
-        # bias term: out0[e,mo,o] = sum_c bias[mo,c] Ut[c,o,e]
+        U16 = U.contiguous().to(torch.bfloat16)
+        # bias term: out0[e,mo,o] = sum_c bias[mo,c] U[c,e,o]
         b16 = bias.detach().to(torch.bfloat16).view(mo, miF)
-        out = (b16 @ Ut16.reshape(miF, O * E)).view(mo, O, E) \
-            .permute(2, 0, 1).contiguous().float()
+        out = (b16 @ U16.view(miF, E * OP)).view(mo, E, OP)[:, :, :O] \
+            .permute(1, 0, 2).contiguous().float()
         hip_bwd = os.environ.get('SE3_TORCH_BWD') != '1'
         # SE3_LOWMEM_PACK=1 trades ~6% step time for memory: save the
         # torch-layout bf16 W (1x) and re-pack in backward, instead of
@@ -159,37 +182,39 @@ class _FusedPairConv(torch.autograd.Function):
             Pf = torch.empty(n128, dtype=torch.bfloat16, device=Wd.device)
             Pdh = torch.empty(n128, dtype=torch.bfloat16, device=Wd.device)
             ext.pack_w_both(Wd, Pf, Pdh, mo)
-            ext.pairconv_fwd(H16, Pf, Ut16, out, mo)
-            ctx.save_for_backward(H16, Pf, Pdh, Ut16, b16)
+            ext.pairconv_fwd_opad(H16, Pf, U16, out, mo)
+            ctx.save_for_backward(H16, Pf, Pdh, U16, b16)
             ctx.packed = True
         else:
             W16 = W.detach().contiguous().to(torch.bfloat16)
-            ext.pairconv_fwd(H16, _pack_w_fwd(W16, mo, miF), Ut16, out, mo)
-            ctx.save_for_backward(H16, W16, Ut16, b16)
+            ext.pairconv_fwd_opad(H16, _pack_w_fwd(W16, mo, miF), U16, out, mo)
+            ctx.save_for_backward(H16, W16, U16, b16)
             ctx.packed = False
         ctx.mo = mo
+        ctx.O = O
         ctx.w_dtype = W.dtype
         ctx.b_dtype = bias.dtype
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        mo = ctx.mo
+        mo, O = ctx.mo, ctx.O
         if ctx.packed:
-            H16, Pf, Pdh, Ut16, b16 = ctx.saved_tensors
+            H16, Pf, Pdh, U16, b16 = ctx.saved_tensors
         else:
-            H16, W16, Ut16, b16 = ctx.saved_tensors
+            H16, W16, U16, b16 = ctx.saved_tensors
         E, K = H16.shape
-        miF, O, _ = Ut16.shape
-        g = grad_out.contiguous()                      # (E, mo, O) fp32
-        g16 = g.to(torch.bfloat16)
+        miF, _, OP = U16.shape
+        g = grad_out.contiguous().float()              # (E, mo, O) fp32
 
         need_H, need_W, need_b, need_u = ctx.needs_input_grad[:4]
 
         ext = _load_ext()
         if os.environ.get('SE3_TORCH_BWD') != '1':
-            dH = dW = db = dUt = None
-            g_t = g16.permute(1, 2, 0).contiguous()    # (mo, O, E) bf16
+            dH = dW = db = dU = None
+            # one pass: cast, transpose and pad, (mo, E, OP) bf16
+            G = torch.empty(mo, E, OP, dtype=torch.bfloat16, device=g.device)
+            ext.pack_g(g, G)
             P1 = Pu = None
             if ctx.packed:
                 P1, Pu = Pdh, Pf
@@ -203,32 +228,33 @@ class _FusedPairConv(torch.autograd.Function):
                 ext.pack_w_both(W16, Pu, P1, mo)
             if need_H:
                 dH = torch.zeros(E, K, dtype=torch.float32, device=H16.device)
-                ext.pairconv_bwd_dh(g_t, Ut16, P1, dH, mo)
+                ext.pairconv_bwd_dh(G, U16, P1, dH, mo, O)
             P1 = None
             if need_W:
                 Ht = H16.t().contiguous()              # (128, E)
                 dW = torch.empty(mo * miF, K, dtype=torch.float32,
                                  device=H16.device)
-                ext.pairconv_bwd_dw(g_t, Ut16, Ht, dW, mo)
+                ext.pairconv_bwd_dw(G, U16, Ht, dW, mo, O)
                 dW = dW.to(ctx.w_dtype)
                 del Ht
             if need_b:
-                # db[(m,c)] = sum_{e,o} g[e,m,o] u[c,o,e] — one GEMM, both
-                # operands are free (mo,O*E)/(miF,O*E) views
-                db = (g_t.reshape(mo, O * E) @ Ut16.reshape(miF, O * E).t()) \
+                # db[(m,c)] = sum_{e,o} g[m,e,o] u[c,e,o] — one GEMM, both
+                # operands are free (mo,E*OP)/(miF,E*OP) views
+                db = (G.view(mo, E * OP) @ U16.view(miF, E * OP).t()) \
                     .reshape(mo * miF).to(ctx.b_dtype)
             if need_u:
-                dUt = torch.empty(miF, O, E, dtype=torch.float32,
-                                  device=H16.device)
+                dU = torch.empty(miF, E, OP, dtype=torch.float32,
+                                 device=H16.device)
                 ext.pairconv_bwd_du(H16, Pu, b16.float().reshape(-1),
-                                    g_t, dUt, mo)
-            return dH, dW, db, dUt, None
+                                    G, dU, mo, O)
+            return dH, dW, db, dU, None, None
 
         if ctx.packed:   # pragma: no cover - env toggled between fwd and bwd
             raise RuntimeError('SE3_TORCH_BWD enabled after a packed forward; '
                                'set it before the forward pass')
-        u_eco = Ut16.permute(2, 0, 1)                  # (E, miF, O) view
-        dH = dW = db = dUt = None
+        g16 = g.to(torch.bfloat16)
+        u_eco = U16[:, :, :O].permute(1, 0, 2)         # (E, miF, O) view
+        dH = dW = db = dU = None
         if need_H:
             dH = torch.zeros(E, K, dtype=torch.float32, device=H16.device)
         if need_W:
@@ -236,7 +262,7 @@ class _FusedPairConv(torch.autograd.Function):
         if need_b:
             db = torch.empty(mo * miF, dtype=torch.float32, device=H16.device)
         if need_u:
-            dUt = torch.zeros(miF, O, E, dtype=torch.float32, device=H16.device)
+            dU = torch.zeros(miF, E, OP, dtype=torch.float32, device=H16.device)
 
         # chunk over mo so the dR slab stays ~<= 1 GiB
         per_mo = E * miF * 2
@@ -254,21 +280,40 @@ class _FusedPairConv(torch.autograd.Function):
             if need_b:
                 db[m0 * miF:m1 * miF] = dR16.float().sum(dim=0)
             if need_u:
-                # R[e,(m,c)] = H @ W^T + bias ; du[c,o,e] += sum_m R * g
+                # R[e,(m,c)] = H @ W^T + bias ; du[c,e,o] += sum_m R * g
                 R = (H16 @ Wslab.t()).view(E, m1 - m0, miF).float() \
                     + b16[m0:m1].float().unsqueeze(0)
-                dUt += torch.einsum('emc,emo->coe', R, g[:, m0:m1])
+                dU[:, :, :O] += torch.einsum('emc,emo->ceo', R, g[:, m0:m1])
             del dR16
 
         if need_W:
             dW = dW.to(ctx.w_dtype)
         if need_b:
             db = db.to(ctx.b_dtype)
-        return dH, dW, db, dUt, None
+        return dH, dW, db, dU, None, None
+
+
+def fused_pairconv_opad(H, W, bias, U, mo, O=None):
+    """Pairwise convolution on U in the o-padded edge-major layout
+    (miF, E, OP(O)) with zero pads; returns (E, mo, O) and differentiates to
+    dU in the same padded shape. O may be omitted where OP decides it
+    (OP 1 -> O 1, OP 4 -> O 3); OP 8 serves O 5 and 7, so say which."""
+    OP = U.shape[2]
+    if O is None:
+        if OP == 8:
+            raise ValueError('U with OP=8 serves O=5 and O=7: pass O')
+        O = {1: 1, 4: 3}[OP]
+    if opad(O) != OP:
+        raise ValueError(f'U has o width {OP}, O={O} needs {opad(O)}')
+    return _FusedPairConvOpad.apply(H, W, bias, U, mo, O)
 
 
 def fused_pairconv(H, W, bias, Ut, mo):
-    return _FusedPairConv.apply(H, W, bias, Ut, mo)
+    """The same on Ut in the e-contiguous (miF, O, E) layout: a
+    differentiable torch repack around fused_pairconv_opad, for producers
+    and callers that do not emit the padded layout themselves."""
+    O = Ut.shape[1]
+    return fused_pairconv_opad(H, W, bias, _to_opad(Ut, O), mo, O)
 
 
 NORM_NONLIN = {'gelu': 0, 'identity': 1}   # selector of csrc/norm_se3.hip
@@ -417,33 +462,35 @@ def fused_attention(q, k, v, mask_u8, n, heads, scale, kv_one=False,
 
 class _UBuildFn(torch.autograd.Function):
     """Basis-feature precontraction (csrc/ubuild.hip):
-    Ut[(c f), o, e] = sum_i B[e,o,i,f] x[e,c,i], emitted directly in the
-    e-contiguous layout the pairconv kernels consume. When the basis
-    requires grad (differentiable_coors) x is saved too and backward also
-    returns dB[e,o,i,f] = sum_c x[e,c,i] dUt[(c f),o,e] in fp32,
-    straight-through for the forward's bf16 rounding. First order only."""
+    U[(c f), e, o] = sum_i B[e,o,i,f] x[e,c,i], emitted directly in the
+    o-padded edge-major layout (C*F, E, OP) the pairconv kernels consume,
+    pad lanes zero. When the basis requires grad (differentiable_coors) x
+    is saved too and backward also returns
+    dB[e,o,i,f] = sum_c x[e,c,i] dU[(c f),e,o] in fp32, straight-through
+    for the forward's bf16 rounding. First order only."""
 
     @staticmethod
     def forward(ctx, x, B, O, I, F):
         ext = _load_ext()
         E, C, _ = x.shape
-        Ut = torch.empty(C * F, O, E, dtype=torch.bfloat16, device=x.device)
+        U = torch.empty(C * F, E, opad(O), dtype=torch.bfloat16,
+                        device=x.device)
         xc = x.contiguous()
-        ext.ubuild_fwd(B, xc, Ut, O, I, F)
+        ext.ubuild_fwd(B, xc, U, O, I, F)
         if ctx.needs_input_grad[1]:
             ctx.save_for_backward(B, xc)
         else:
             ctx.save_for_backward(B)
         ctx.meta = (x.dtype, x.shape, O, I, F)
-        return Ut
+        return U
 
     @staticmethod
     @torch.autograd.function.once_differentiable
-    def backward(ctx, dUt):
+    def backward(ctx, dU):
         ext = _load_ext()
         B = ctx.saved_tensors[0]
         dtype, (E, C, I_), O, I, F = ctx.meta
-        dU = dUt.contiguous().float()
+        dU = dU.contiguous().float()                   # (C*F, E, OP)
         dX = dB = None
         if ctx.needs_input_grad[0]:
             dX = torch.empty(E, C, I, dtype=dtype, device=B.device)
@@ -459,8 +506,14 @@ def ubuild_ok(B, C, O, I, F) -> bool:
             and C % 32 == 0 and O * I * F <= 343)
 
 
-def ubuild(x, B, O, I, F):
+def ubuild_opad(x, B, O, I, F):
+    """U (C*F, E, OP(O)) bf16, zero pads: what fused_pairconv_opad reads."""
     return _UBuildFn.apply(x, B, O, I, F)
+
+
+def ubuild(x, B, O, I, F):
+    """The e-contiguous (C*F, O, E) contract, as a view of ubuild_opad."""
+    return ubuild_opad(x, B, O, I, F)[:, :, :O].permute(0, 2, 1)
 
 
 class _HtypeRelDistFn(torch.autograd.Function):
