@@ -31,9 +31,9 @@
 // masked key never passes gradient to q or k, in any row, because no
 // gradient passes the fill.
 
-#include <torch/extension.h>
 #include <hip/hip_runtime.h>
-#include <ATen/hip/HIPContext.h>
+#include "host_common.h"
+#include "ops.h"
 #include <hip/hip_bf16.h>
 
 #define NTA2 256  // 4 waves (= 4 query rows) per block
@@ -342,26 +342,16 @@ void attn2_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
     const unsigned char* mp = opt_mask(mask);
     const float* qfp = opt_f32(qf);
     const float* kfp = opt_f32(kf);
-#define A2_LAUNCH_F(T)                                                          \
-    A2_DISPATCH(T, DT, {                                                        \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(attn2_fwd_kernel<T, kDT>),           \
-                           grid, dim3(NTA2), 0, stream,                         \
-                           reinterpret_cast<const T*>(q.data_ptr()),            \
-                           reinterpret_cast<const T*>(k.data_ptr()),            \
-                           reinterpret_cast<const T*>(v.data_ptr()),            \
-                           mp, qfp, kfp, out.data_ptr<float>(),                 \
-                           lse.data_ptr<float>(), R, J, DM, (int)n,             \
-                           (int)heads, (float)scale, kv_one ? 1 : 0,            \
-                           (int)jr, (int)rot);                                  \
-    })
-    if (q.dtype() == torch::kFloat32) { A2_LAUNCH_F(float); }
-    else {
-        TORCH_CHECK(q.dtype() == torch::kBFloat16);
-        A2_LAUNCH_F(__hip_bfloat16);
-    }
-#undef A2_LAUNCH_F
-    hipError_t err = hipGetLastError();
-    TORCH_CHECK(err == hipSuccess, "attn2_fwd: ", hipGetErrorString(err));
+    DISPATCH_F32_BF16(q, __hip_bfloat16, A2_DISPATCH(T, DT, {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(attn2_fwd_kernel<T, kDT>),
+                           grid, dim3(NTA2), 0, stream,
+                           tptr<const T>(q), tptr<const T>(k), tptr<const T>(v),
+                           mp, qfp, kfp, out.data_ptr<float>(),
+                           lse.data_ptr<float>(), R, J, DM, (int)n,
+                           (int)heads, (float)scale, kv_one ? 1 : 0,
+                           (int)jr, (int)rot);
+    }));
+    check_launch("attn2_fwd: ");
 }
 
 void attn2_bwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
@@ -381,13 +371,11 @@ void attn2_bwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
     const unsigned char* mp = opt_mask(mask);
     const float* qfp = opt_f32(qf);
     const float* kfp = opt_f32(kf);
-#define A2_LAUNCH_B(T, AT)                                                      \
+#define A2_LAUNCH_B(AT)                                                         \
     A2_DISPATCH(T, DT, {                                                        \
         hipLaunchKernelGGL(HIP_KERNEL_NAME(attn2_bwd_kernel<T, kDT, AT>),       \
                            grid, dim3(NTA2), 0, stream,                         \
-                           reinterpret_cast<const T*>(q.data_ptr()),            \
-                           reinterpret_cast<const T*>(k.data_ptr()),            \
-                           reinterpret_cast<const T*>(v.data_ptr()),            \
+                           tptr<const T>(q), tptr<const T>(k), tptr<const T>(v),\
                            mp, qfp, kfp, out.data_ptr<float>(),                 \
                            lse.data_ptr<float>(), g.data_ptr<float>(),          \
                            dq.data_ptr<float>(), dk.data_ptr<float>(),          \
@@ -395,15 +383,10 @@ void attn2_bwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                            (int)heads, (float)scale, kv_one ? 1 : 0,            \
                            (int)jr, (int)rot);                                  \
     })
-    if (q.dtype() == torch::kFloat32) {
-        if (kv_one) { A2_LAUNCH_B(float, true); }
-        else { A2_LAUNCH_B(float, false); }
-    } else {
-        TORCH_CHECK(q.dtype() == torch::kBFloat16);
-        if (kv_one) { A2_LAUNCH_B(__hip_bfloat16, true); }
-        else { A2_LAUNCH_B(__hip_bfloat16, false); }
-    }
+    DISPATCH_F32_BF16(q, __hip_bfloat16, {
+        if (kv_one) { A2_LAUNCH_B(true); }
+        else { A2_LAUNCH_B(false); }
+    });
 #undef A2_LAUNCH_B
-    hipError_t err = hipGetLastError();
-    TORCH_CHECK(err == hipSuccess, "attn2_bwd: ", hipGetErrorString(err));
+    check_launch("attn2_bwd: ");
 }

@@ -16,9 +16,9 @@
 // Backward: per-(i,j,d) recompute of rel/u; dhtype needs a scatter-add to
 // the neighbor rows (atomic f32); dscale/dbias accumulate per-d atomics.
 
-#include <torch/extension.h>
 #include <hip/hip_runtime.h>
-#include <ATen/hip/HIPContext.h>
+#include "host_common.h"
+#include "ops.h"
 
 #define EG_NT 256
 #define EG_MAXM 7
@@ -189,14 +189,6 @@ static long eg_grid(long total) {
     return gb > 1048576 ? 1048576 : gb;
 }
 
-#define EG_DTYPE(ht, ...)                                              \
-    if (ht.dtype() == torch::kFloat32) {                               \
-        using T = float; __VA_ARGS__;                                  \
-    } else {                                                           \
-        TORCH_CHECK(ht.dtype() == torch::kBFloat16);                   \
-        using T = __bf16; __VA_ARGS__;                                 \
-    }
-
 void egnn_rel_dist_fwd(torch::Tensor ht, torch::Tensor idx, torch::Tensor dist) {
     int b = ht.size(0), n = ht.size(1), d = ht.size(2), m = ht.size(3);
     int k = idx.size(2);
@@ -204,15 +196,14 @@ void egnn_rel_dist_fwd(torch::Tensor ht, torch::Tensor idx, torch::Tensor dist) 
                 dist.is_contiguous() && m <= EG_MAXM);
     long total = (long)b * n * k * d;
     auto stream = at::cuda::getCurrentHIPStream();
-    EG_DTYPE(ht, {
+    DISPATCH_F32_BF16(ht, __bf16, {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(egnn_rel_dist_fwd_kernel<T>),
                            dim3(eg_grid(total)), dim3(EG_NT), 0, stream,
-                           reinterpret_cast<const T*>(ht.data_ptr()),
+                           tptr<const T>(ht),
                            idx.data_ptr<long>(), dist.data_ptr<float>(),
                            total, n, k, d, m);
     });
-    hipError_t err = hipGetLastError();
-    TORCH_CHECK(err == hipSuccess, "egnn_rel_dist_fwd: ", hipGetErrorString(err));
+    check_launch("egnn_rel_dist_fwd: ");
 }
 
 void egnn_rel_dist_bwd(torch::Tensor ht, torch::Tensor idx, torch::Tensor gdist,
@@ -223,15 +214,14 @@ void egnn_rel_dist_bwd(torch::Tensor ht, torch::Tensor idx, torch::Tensor gdist,
                 dht.dtype() == torch::kFloat32);
     long total = (long)b * n * k * d;
     auto stream = at::cuda::getCurrentHIPStream();
-    EG_DTYPE(ht, {
+    DISPATCH_F32_BF16(ht, __bf16, {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(egnn_rel_dist_bwd_kernel<T>),
                            dim3(eg_grid(total)), dim3(EG_NT), 0, stream,
-                           reinterpret_cast<const T*>(ht.data_ptr()),
+                           tptr<const T>(ht),
                            idx.data_ptr<long>(), gdist.data_ptr<float>(),
                            dht.data_ptr<float>(), total, n, k, d, m);
     });
-    hipError_t err = hipGetLastError();
-    TORCH_CHECK(err == hipSuccess, "egnn_rel_dist_bwd: ", hipGetErrorString(err));
+    check_launch("egnn_rel_dist_bwd: ");
 }
 
 void egnn_htype_update_fwd(torch::Tensor ht, torch::Tensor idx, torch::Tensor w,
@@ -244,16 +234,15 @@ void egnn_htype_update_fwd(torch::Tensor ht, torch::Tensor idx, torch::Tensor w,
     TORCH_CHECK(w.dtype() == torch::kFloat32 && sc.numel() == d && bi.numel() == d);
     long total = (long)b * n * d;
     auto stream = at::cuda::getCurrentHIPStream();
-    EG_DTYPE(ht, {
+    DISPATCH_F32_BF16(ht, __bf16, {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(egnn_htype_update_fwd_kernel<T>),
                            dim3(eg_grid(total)), dim3(EG_NT), 0, stream,
-                           reinterpret_cast<const T*>(ht.data_ptr()),
+                           tptr<const T>(ht),
                            idx.data_ptr<long>(), w.data_ptr<float>(),
                            sc.data_ptr<float>(), bi.data_ptr<float>(),
                            upd.data_ptr<float>(), total, n, k, d, m, (float)eps);
     });
-    hipError_t err = hipGetLastError();
-    TORCH_CHECK(err == hipSuccess, "egnn_htype_update_fwd: ", hipGetErrorString(err));
+    check_launch("egnn_htype_update_fwd: ");
 }
 
 void egnn_htype_update_bwd(torch::Tensor ht, torch::Tensor idx, torch::Tensor w,
@@ -265,16 +254,15 @@ void egnn_htype_update_bwd(torch::Tensor ht, torch::Tensor idx, torch::Tensor w,
     TORCH_CHECK(g.is_contiguous() && dht.is_contiguous() && dw.is_contiguous());
     long total = (long)b * n * k * d;
     auto stream = at::cuda::getCurrentHIPStream();
-    EG_DTYPE(ht, {
+    DISPATCH_F32_BF16(ht, __bf16, {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(egnn_htype_update_bwd_kernel<T>),
                            dim3(eg_grid(total)), dim3(EG_NT), 0, stream,
-                           reinterpret_cast<const T*>(ht.data_ptr()),
+                           tptr<const T>(ht),
                            idx.data_ptr<long>(), w.data_ptr<float>(),
                            sc.data_ptr<float>(), bi.data_ptr<float>(),
                            g.data_ptr<float>(), dht.data_ptr<float>(),
                            dw.data_ptr<float>(), dsc.data_ptr<float>(),
                            dbi.data_ptr<float>(), total, n, k, d, m, (float)eps);
     });
-    hipError_t err = hipGetLastError();
-    TORCH_CHECK(err == hipSuccess, "egnn_htype_update_bwd: ", hipGetErrorString(err));
+    check_launch("egnn_htype_update_bwd: ");
 }

@@ -28,12 +28,12 @@
 // Invalid slots emit index 0/1 with ZERO geometry (consumers that ignore
 // the mask see no fabricated edge).
 
-#include <torch/extension.h>
 #include <hip/hip_runtime.h>
-#include <ATen/hip/HIPContext.h>
+#include "host_common.h"
+#include "ops.h"
 
 // dynamic LDS a launch may ask for without hipFuncSetAttribute; mirrored by
-// KNN_MAX_LDS in ops/fused.py and checked against it on first use
+// KNN_MAX_LDS in ops/fused.py and checked against it when the extension loads
 #define KNN_MAX_LDS_BYTES 65536
 
 __global__ void __launch_bounds__(64)
@@ -208,6 +208,5 @@ void knn_graph(torch::Tensor coors, torch::Tensor nmask, torch::Tensor allow,
                        dist.data_ptr<float>(), rel.data_ptr<float>(),
                        m.data_ptr<unsigned char>(), b, n, (int)k, L,
                        (float)radius, causal ? 1 : 0);
-    hipError_t err = hipGetLastError();
-    TORCH_CHECK(err == hipSuccess, "knn_graph: ", hipGetErrorString(err));
+    check_launch("knn_graph: ");
 }

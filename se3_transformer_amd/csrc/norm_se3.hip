@@ -26,9 +26,9 @@
 // dW = nu^T @ dgate with one library GEMM: deterministic, no atomics.
 // Exact-erf GELU matches torch.nn.GELU; all math in fp32 registers.
 
-#include <torch/extension.h>
 #include <hip/hip_runtime.h>
-#include <ATen/hip/HIPContext.h>
+#include "host_common.h"
+#include "ops.h"
 #include <hip/hip_bf16.h>
 
 #define NTN 256
@@ -274,15 +274,6 @@ norm_se3_gated_bwd_kernel(const T* __restrict__ t, const float* __restrict__ Wt,
     }
 }
 
-#define DISPATCH_M(M, ...)                                        \
-    switch (M) {                                                  \
-        case 1: { constexpr int kM = 1; __VA_ARGS__; break; }     \
-        case 3: { constexpr int kM = 3; __VA_ARGS__; break; }     \
-        case 5: { constexpr int kM = 5; __VA_ARGS__; break; }     \
-        case 7: { constexpr int kM = 7; __VA_ARGS__; break; }     \
-        default: TORCH_CHECK(false, "unsupported order ", M);     \
-    }
-
 #define DISPATCH_NL(NL, ...)                                      \
     switch (NL) {                                                 \
         case 0: { constexpr int kNL = 0; __VA_ARGS__; break; }    \
@@ -290,7 +281,10 @@ norm_se3_gated_bwd_kernel(const T* __restrict__ t, const float* __restrict__ Wt,
         default: TORCH_CHECK(false, "unsupported nonlinearity ", NL); \
     }
 
-using bf16 = __hip_bfloat16;
+// Body runs with T (float | bf16), kM (order) and kNL (nonlinearity) bound.
+#define DISPATCH_NORM(t, M, nonlin, ...)                          \
+    DISPATCH_NL(nonlin, DISPATCH_ORDER(M, kM, "order",            \
+        DISPATCH_F32_BF16(t, __hip_bfloat16, __VA_ARGS__)))
 
 void norm_se3_nl_fwd(torch::Tensor t, torch::Tensor scale, torch::Tensor out,
                      double eps, int64_t nonlin) {
@@ -303,24 +297,13 @@ void norm_se3_nl_fwd(torch::Tensor t, torch::Tensor scale, torch::Tensor out,
     if (rows == 0) return;
     auto stream = at::cuda::getCurrentHIPStream();
     dim3 grid((rows + NTN - 1) / NTN);
-    DISPATCH_NL(nonlin, DISPATCH_M(M, {
-        if (t.dtype() == torch::kFloat32) {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(norm_se3_fwd_kernel<float, kM, kNL>),
-                               grid, dim3(NTN), 0, stream,
-                               t.data_ptr<float>(), scale.data_ptr<float>(),
-                               out.data_ptr<float>(), rows, C, (float)eps);
-        } else {
-            TORCH_CHECK(t.dtype() == torch::kBFloat16);
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(norm_se3_fwd_kernel<bf16, kM, kNL>),
-                               grid, dim3(NTN), 0, stream,
-                               reinterpret_cast<const bf16*>(t.data_ptr()),
-                               scale.data_ptr<float>(),
-                               reinterpret_cast<bf16*>(out.data_ptr()),
-                               rows, C, (float)eps);
-        }
-    }));
-    hipError_t err = hipGetLastError();
-    TORCH_CHECK(err == hipSuccess, "norm_se3_fwd: ", hipGetErrorString(err));
+    DISPATCH_NORM(t, M, nonlin, {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(norm_se3_fwd_kernel<T, kM, kNL>),
+                           grid, dim3(NTN), 0, stream,
+                           tptr<const T>(t), scale.data_ptr<float>(),
+                           tptr<T>(out), rows, C, (float)eps);
+    });
+    check_launch("norm_se3_fwd: ");
 }
 
 void norm_se3_nl_bwd(torch::Tensor t, torch::Tensor scale, torch::Tensor dout,
@@ -339,26 +322,14 @@ void norm_se3_nl_bwd(torch::Tensor t, torch::Tensor scale, torch::Tensor dout,
     if (rows == 0) return;
     auto stream = at::cuda::getCurrentHIPStream();
     dim3 grid((rows + NTN - 1) / NTN);
-    DISPATCH_NL(nonlin, DISPATCH_M(M, {
-        if (t.dtype() == torch::kFloat32) {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(norm_se3_bwd_kernel<float, kM, kNL>),
-                               grid, dim3(NTN), 0, stream,
-                               t.data_ptr<float>(), scale.data_ptr<float>(),
-                               dout.data_ptr<float>(), dt.data_ptr<float>(),
-                               dscale.data_ptr<float>(), rows, C, (float)eps);
-        } else {
-            TORCH_CHECK(t.dtype() == torch::kBFloat16);
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(norm_se3_bwd_kernel<bf16, kM, kNL>),
-                               grid, dim3(NTN), 0, stream,
-                               reinterpret_cast<const bf16*>(t.data_ptr()),
-                               scale.data_ptr<float>(),
-                               reinterpret_cast<const bf16*>(dout.data_ptr()),
-                               reinterpret_cast<bf16*>(dt.data_ptr()),
-                               dscale.data_ptr<float>(), rows, C, (float)eps);
-        }
-    }));
-    hipError_t err = hipGetLastError();
-    TORCH_CHECK(err == hipSuccess, "norm_se3_bwd: ", hipGetErrorString(err));
+    DISPATCH_NORM(t, M, nonlin, {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(norm_se3_bwd_kernel<T, kM, kNL>),
+                           grid, dim3(NTN), 0, stream,
+                           tptr<const T>(t), scale.data_ptr<float>(),
+                           tptr<const T>(dout), tptr<T>(dt),
+                           dscale.data_ptr<float>(), rows, C, (float)eps);
+    });
+    check_launch("norm_se3_bwd: ");
 }
 
 int64_t norm_se3_gated_max_c() { return GATED_MAX_C; }
@@ -387,27 +358,14 @@ void norm_se3_gated_fwd(torch::Tensor t, torch::Tensor W, torch::Tensor out,
     auto stream = at::cuda::getCurrentHIPStream();
     dim3 grid((N + GR - 1) / GR);
     size_t lds = (size_t)C * GR * sizeof(float);
-    DISPATCH_NL(nonlin, DISPATCH_M(M, {
-        if (t.dtype() == torch::kFloat32) {
-            hipLaunchKernelGGL(
-                HIP_KERNEL_NAME(norm_se3_gated_fwd_kernel<float, kM, kNL>),
-                grid, dim3(NTN), lds, stream,
-                t.data_ptr<float>(), W.data_ptr<float>(),
-                out.data_ptr<float>(), gate.data_ptr<float>(),
-                N, C, (float)eps);
-        } else {
-            TORCH_CHECK(t.dtype() == torch::kBFloat16);
-            hipLaunchKernelGGL(
-                HIP_KERNEL_NAME(norm_se3_gated_fwd_kernel<bf16, kM, kNL>),
-                grid, dim3(NTN), lds, stream,
-                reinterpret_cast<const bf16*>(t.data_ptr()),
-                W.data_ptr<float>(),
-                reinterpret_cast<bf16*>(out.data_ptr()),
-                gate.data_ptr<float>(), N, C, (float)eps);
-        }
-    }));
-    hipError_t err = hipGetLastError();
-    TORCH_CHECK(err == hipSuccess, "norm_se3_gated_fwd: ", hipGetErrorString(err));
+    DISPATCH_NORM(t, M, nonlin, {
+        hipLaunchKernelGGL(
+            HIP_KERNEL_NAME(norm_se3_gated_fwd_kernel<T, kM, kNL>),
+            grid, dim3(NTN), lds, stream,
+            tptr<const T>(t), W.data_ptr<float>(), tptr<T>(out),
+            gate.data_ptr<float>(), N, C, (float)eps);
+    });
+    check_launch("norm_se3_gated_fwd: ");
 }
 
 // Wt is w_gate transposed ([e, d], contiguous); dgate and nu come back as
@@ -435,28 +393,13 @@ void norm_se3_gated_bwd(torch::Tensor t, torch::Tensor Wt, torch::Tensor gate,
     auto stream = at::cuda::getCurrentHIPStream();
     dim3 grid((N + GR - 1) / GR);
     size_t lds = (size_t)C * GR * sizeof(float);
-    DISPATCH_NL(nonlin, DISPATCH_M(M, {
-        if (t.dtype() == torch::kFloat32) {
-            hipLaunchKernelGGL(
-                HIP_KERNEL_NAME(norm_se3_gated_bwd_kernel<float, kM, kNL>),
-                grid, dim3(NTN), lds, stream,
-                t.data_ptr<float>(), Wt.data_ptr<float>(),
-                gate.data_ptr<float>(), dout.data_ptr<float>(),
-                dt.data_ptr<float>(), dgate.data_ptr<float>(),
-                nu.data_ptr<float>(), N, C, (float)eps);
-        } else {
-            TORCH_CHECK(t.dtype() == torch::kBFloat16);
-            hipLaunchKernelGGL(
-                HIP_KERNEL_NAME(norm_se3_gated_bwd_kernel<bf16, kM, kNL>),
-                grid, dim3(NTN), lds, stream,
-                reinterpret_cast<const bf16*>(t.data_ptr()),
-                Wt.data_ptr<float>(), gate.data_ptr<float>(),
-                reinterpret_cast<const bf16*>(dout.data_ptr()),
-                reinterpret_cast<bf16*>(dt.data_ptr()),
-                dgate.data_ptr<float>(), nu.data_ptr<float>(),
-                N, C, (float)eps);
-        }
-    }));
-    hipError_t err = hipGetLastError();
-    TORCH_CHECK(err == hipSuccess, "norm_se3_gated_bwd: ", hipGetErrorString(err));
+    DISPATCH_NORM(t, M, nonlin, {
+        hipLaunchKernelGGL(
+            HIP_KERNEL_NAME(norm_se3_gated_bwd_kernel<T, kM, kNL>),
+            grid, dim3(NTN), lds, stream,
+            tptr<const T>(t), Wt.data_ptr<float>(), gate.data_ptr<float>(),
+            tptr<const T>(dout), tptr<T>(dt), dgate.data_ptr<float>(),
+            nu.data_ptr<float>(), N, C, (float)eps);
+    });
+    check_launch("norm_se3_gated_bwd: ");
 }

@@ -16,9 +16,9 @@
 // Block = one (m, cb) tile: 32 rows (c) x 128 cols (k), staged in LDS as
 // bf16 with a 16B-slot XOR swizzle so phase-2 reads are conflict-light.
 
-#include <torch/extension.h>
 #include <hip/hip_runtime.h>
-#include <ATen/hip/HIPContext.h>
+#include "host_common.h"
+#include "ops.h"
 #include "pairconv_common.h"
 
 #define NTP 256
@@ -90,20 +90,12 @@ void pack_w_both(torch::Tensor W, torch::Tensor Pf, torch::Tensor Pdh, int64_t m
     TORCH_CHECK(Pf.numel() == N * 128 && Pdh.numel() == N * 128);
     auto stream = at::cuda::getCurrentHIPStream();
     dim3 grid((long)mo * (miF / 32));
-    if (W.dtype() == torch::kFloat32) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(pack_w_kernel<float>), grid, dim3(NTP), 0, stream,
-                           W.data_ptr<float>(),
-                           reinterpret_cast<__bf16*>(Pf.data_ptr()),
-                           reinterpret_cast<__bf16*>(Pdh.data_ptr()), mo, miF);
-    } else {
-        TORCH_CHECK(W.dtype() == torch::kBFloat16);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(pack_w_kernel<__bf16>), grid, dim3(NTP), 0, stream,
-                           reinterpret_cast<const __bf16*>(W.data_ptr()),
-                           reinterpret_cast<__bf16*>(Pf.data_ptr()),
-                           reinterpret_cast<__bf16*>(Pdh.data_ptr()), mo, miF);
-    }
-    hipError_t err = hipGetLastError();
-    TORCH_CHECK(err == hipSuccess, "pack_w_both: ", hipGetErrorString(err));
+    DISPATCH_F32_BF16(W, __bf16, {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(pack_w_kernel<T>), grid, dim3(NTP), 0, stream,
+                           tptr<const T>(W), tptr<__bf16>(Pf), tptr<__bf16>(Pdh),
+                           mo, miF);
+    });
+    check_launch("pack_w_both: ");
 }
 
 // ---------------------------------------------------------------------------
@@ -159,9 +151,8 @@ void pack_g(torch::Tensor grad, torch::Tensor G) {
     if (E == 0 || mo == 0) return;
     auto stream = at::cuda::getCurrentHIPStream();
     dim3 grid((E + PG_E - 1) / PG_E, (mo + PG_M - 1) / PG_M);
-    DISPATCH_O(O, hipLaunchKernelGGL(HIP_KERNEL_NAME(pack_g_kernel<kO>), grid,
-                                     dim3(NTP), 0, stream, grad.data_ptr<float>(),
-                                     reinterpret_cast<__bf16*>(G.data_ptr()), E, mo));
-    hipError_t err = hipGetLastError();
-    TORCH_CHECK(err == hipSuccess, "pack_g: ", hipGetErrorString(err));
+    DISPATCH_ORDER(O, kO, "O", hipLaunchKernelGGL(
+        HIP_KERNEL_NAME(pack_g_kernel<kO>), grid, dim3(NTP), 0, stream,
+        grad.data_ptr<float>(), tptr<__bf16>(G), E, mo));
+    check_launch("pack_g: ");
 }

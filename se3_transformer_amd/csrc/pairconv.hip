@@ -34,6 +34,7 @@
 
 #include <hip/hip_runtime.h>
 #include "pairconv_common.h"
+#include "ops.h"
 
 #define BLK_E 64
 #define BLK_MO 8
@@ -292,9 +293,8 @@ static void launch_fwd(const torch::Tensor& H, const torch::Tensor& P,
     hipLaunchKernelGGL(HIP_KERNEL_NAME(pairconv_fwd_kernel<O, MB2, WP, UNR>),
                        dim3(nmemb * ng), dim3(NT), lds,
                        at::cuda::getCurrentHIPStream(),
-                       reinterpret_cast<const __bf16*>(H.data_ptr()),
-                       reinterpret_cast<const __bf16*>(P.data_ptr()),
-                       reinterpret_cast<const __bf16*>(Ut.data_ptr()),
+                       tptr<const __bf16>(H), tptr<const __bf16>(P),
+                       tptr<const __bf16>(Ut),
                        out.data_ptr<float>(), E, mo, miF, nmemb, coh);
 }
 
@@ -321,139 +321,9 @@ void pairconv_fwd_opad(torch::Tensor H, torch::Tensor W, torch::Tensor Ut,
     TORCH_CHECK(out.size(0) == E && out.size(1) == mo);
     TORCH_CHECK(miF % UCHUNK == 0, "miF must be a multiple of 32");
     TORCH_CHECK(mo % BLK_MO == 0, "mo must be a multiple of 8");
-    DISPATCH_O(O, {
+    DISPATCH_ORDER(O, kO, "O", {
         if (mo % (BLK_MO * 2) == 0) launch_fwd<kO, 2>(H, W, Ut, out, E, mo, miF);
         else launch_fwd<kO, 1>(H, W, Ut, out, E, mo, miF);
     });
-    hipError_t err = hipGetLastError();
-    TORCH_CHECK(err == hipSuccess, "pairconv_fwd launch failed: ", hipGetErrorString(err));
-}
-
-// The (miF, O, E) entry kept for callers of the e-contiguous layout: repack
-// to (miF, E, OP) with zero pads, then the kernel above.
-void pairconv_fwd(torch::Tensor H, torch::Tensor W, torch::Tensor Ut,
-                  torch::Tensor out, int64_t mo_) {
-    TORCH_CHECK(Ut.dim() == 3 && out.dim() == 3 && Ut.size(1) == out.size(2));
-    int O = Ut.size(1);
-    TORCH_CHECK(O == 1 || O == 3 || O == 5 || O == 7, "unsupported O ", O);
-    auto U = at::constant_pad_nd(Ut.permute({0, 2, 1}), {0, opad_of(O) - O}).contiguous();
-    pairconv_fwd_opad(H, W, U, out, mo_);
-}
-
-void sh_basis_fwd(torch::Tensor rel, torch::Tensor qcat, torch::Tensor normtab,
-                  torch::Tensor meta, torch::Tensor out, int64_t L);
-void knn_graph(torch::Tensor coors, torch::Tensor nmask, torch::Tensor allow,
-               torch::Tensor sparse, torch::Tensor idx,
-               torch::Tensor dist, torch::Tensor rel, torch::Tensor m,
-               int64_t k, double radius, bool causal);
-int64_t knn_max_lds_bytes();
-void attn2_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
-               torch::Tensor mask, torch::Tensor qf, torch::Tensor kf,
-               torch::Tensor out, torch::Tensor lse,
-               int64_t n, int64_t heads, double scale, bool kv_one,
-               int64_t jr, int64_t rot);
-void attn2_bwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
-               torch::Tensor mask, torch::Tensor qf, torch::Tensor kf,
-               torch::Tensor out, torch::Tensor lse, torch::Tensor g,
-               torch::Tensor dq, torch::Tensor dk, torch::Tensor dv,
-               int64_t n, int64_t heads, double scale, bool kv_one,
-               int64_t jr, int64_t rot);
-void norm_se3_nl_fwd(torch::Tensor t, torch::Tensor scale, torch::Tensor out,
-                     double eps, int64_t nonlin);
-void norm_se3_nl_bwd(torch::Tensor t, torch::Tensor scale, torch::Tensor dout,
-                     torch::Tensor dt, torch::Tensor dscale, double eps,
-                     int64_t nonlin);
-int64_t norm_se3_gated_max_c();
-void norm_se3_gated_fwd(torch::Tensor t, torch::Tensor W, torch::Tensor out,
-                        torch::Tensor gate, double eps, int64_t nonlin);
-void norm_se3_gated_bwd(torch::Tensor t, torch::Tensor Wt, torch::Tensor gate,
-                        torch::Tensor dout, torch::Tensor dt,
-                        torch::Tensor dgate, torch::Tensor nu, double eps,
-                        int64_t nonlin);
-void pairconv_bwd_dh(torch::Tensor G, torch::Tensor U, torch::Tensor Wt,
-                     torch::Tensor dH, int64_t mo_, int64_t O_);
-void pairconv_bwd_dw(torch::Tensor G, torch::Tensor U, torch::Tensor Ht,
-                     torch::Tensor dW, int64_t mo_, int64_t O_);
-void pairconv_bwd_du(torch::Tensor H, torch::Tensor W, torch::Tensor bias,
-                     torch::Tensor G, torch::Tensor dU, int64_t mo_, int64_t O_);
-void pack_w_both(torch::Tensor W, torch::Tensor Pf, torch::Tensor Pdh, int64_t mo_);
-void pack_g(torch::Tensor grad, torch::Tensor G);
-void ubuild_fwd(torch::Tensor B, torch::Tensor X, torch::Tensor U,
-                int64_t O, int64_t I, int64_t F);
-void ubuild_bwd_dx(torch::Tensor B, torch::Tensor dU, torch::Tensor dX,
-                   int64_t O, int64_t I, int64_t F);
-void ubuild_bwd_db(torch::Tensor X, torch::Tensor dU, torch::Tensor dB,
-                   int64_t O, int64_t I, int64_t F);
-void sh_basis_bwd(torch::Tensor rel, torch::Tensor qcat, torch::Tensor normtab,
-                  torch::Tensor meta, torch::Tensor dK, torch::Tensor drel,
-                  int64_t L);
-void egnn_rel_dist_fwd(torch::Tensor ht, torch::Tensor idx, torch::Tensor dist);
-void egnn_rel_dist_bwd(torch::Tensor ht, torch::Tensor idx, torch::Tensor gdist,
-                       torch::Tensor dht);
-void egnn_htype_update_fwd(torch::Tensor ht, torch::Tensor idx, torch::Tensor w,
-                           torch::Tensor sc, torch::Tensor bi,
-                           torch::Tensor upd, double eps);
-void egnn_htype_update_bwd(torch::Tensor ht, torch::Tensor idx, torch::Tensor w,
-                           torch::Tensor sc, torch::Tensor bi, torch::Tensor g,
-                           torch::Tensor dht, torch::Tensor dw,
-                           torch::Tensor dsc, torch::Tensor dbi, double eps);
-void radial_trunk_fwd(torch::Tensor X, torch::Tensor W0, torch::Tensor p0,
-                      torch::Tensor W3, torch::Tensor p3,
-                      torch::Tensor H, torch::Tensor yh0, torch::Tensor yh3,
-                      torch::Tensor rs01, double eps);
-void radial_trunk_bwd(torch::Tensor dH, torch::Tensor X, torch::Tensor W0,
-                      torch::Tensor p0, torch::Tensor W3, torch::Tensor W3t,
-                      torch::Tensor p3, torch::Tensor yh0, torch::Tensor yh3,
-                      torch::Tensor rs01, torch::Tensor dW0, torch::Tensor dp0,
-                      torch::Tensor dW3, torch::Tensor dp3, torch::Tensor dX,
-                      double eps);
-
-PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
-    m.def("pairconv_fwd", &pairconv_fwd,
-          "fused radial-GEMM + basis contraction forward (MI355X)");
-    m.def("pairconv_fwd_opad", &pairconv_fwd_opad,
-          "the same on U in the (miF, E, OP) o-padded edge-major layout");
-    m.def("pairconv_opad", &pairconv_opad, "padded o width OP(O)");
-    m.def("pack_g", &pack_g,
-          "grad_out (E, mo, O) f32 -> G (mo, E, OP) bf16, zero pads");
-    m.def("pairconv_bwd_dh", &pairconv_bwd_dh, "dH backward");
-    m.def("pairconv_bwd_dw", &pairconv_bwd_dw, "dW backward");
-    m.def("pairconv_bwd_du", &pairconv_bwd_du, "dU backward");
-    m.def("knn_graph", &knn_graph, "on-device kNN graph build");
-    m.def("knn_max_lds_bytes", &knn_max_lds_bytes,
-          "dynamic-LDS ceiling of the kNN kernel (bounds n and k)");
-    m.def("attn2_fwd", &attn2_fwd,
-          "fused neighbor attention fwd (online softmax, in-kernel rotary)");
-    m.def("attn2_bwd", &attn2_bwd, "fused neighbor attention backward");
-    m.def("norm_se3_nl_fwd", &norm_se3_nl_fwd,
-          "fused NormSE3 forward, nonlin 0 = GELU, 1 = identity");
-    m.def("norm_se3_nl_bwd", &norm_se3_nl_bwd,
-          "fused NormSE3 backward, nonlin 0 = GELU, 1 = identity");
-    m.def("norm_se3_gated_max_c", &norm_se3_gated_max_c,
-          "channel ceiling of the gated-scale NormSE3 kernels");
-    m.def("norm_se3_gated_fwd", &norm_se3_gated_fwd,
-          "fused gated-scale NormSE3 forward (also writes gate)");
-    m.def("norm_se3_gated_bwd", &norm_se3_gated_bwd,
-          "fused gated-scale NormSE3 backward (dt; dgate and nu for dW)");
-    m.def("sh_basis_fwd", &sh_basis_fwd,
-          "fused spherical-harmonics + equivariant basis (MI355X)");
-    m.def("pack_w_both", &pack_w_both,
-          "one-pass pack of net.6 W into both MFMA fragment layouts");
-    m.def("radial_trunk_fwd", &radial_trunk_fwd,
-          "fused radial trunk (Linear-LN-GELU x2) forward");
-    m.def("radial_trunk_bwd", &radial_trunk_bwd,
-          "fused radial trunk backward");
-    m.def("ubuild_fwd", &ubuild_fwd,
-          "basis x features precontraction, out (C*F, E, OP)");
-    m.def("ubuild_bwd_dx", &ubuild_bwd_dx, "ubuild dX backward");
-    m.def("ubuild_bwd_db", &ubuild_bwd_db,
-          "ubuild dB backward (differentiable coordinates)");
-    m.def("sh_basis_bwd", &sh_basis_bwd,
-          "fused spherical-harmonics + basis backward: dK -> d rel");
-    m.def("egnn_rel_dist_fwd", &egnn_rel_dist_fwd,
-          "EGNN neighbor rel-htype distances (no n^2 intermediate)");
-    m.def("egnn_rel_dist_bwd", &egnn_rel_dist_bwd, "its backward");
-    m.def("egnn_htype_update_fwd", &egnn_htype_update_fwd,
-          "EGNN htype norm+weighted neighbor sum (no n^2 intermediate)");
-    m.def("egnn_htype_update_bwd", &egnn_htype_update_bwd, "its backward");
+    check_launch("pairconv_fwd launch failed: ");
 }

@@ -20,6 +20,7 @@
 
 #include <hip/hip_runtime.h>
 #include "pairconv_common.h"
+#include "ops.h"
 
 // ---------------------------------------------------------------------------
 // B1: dH[e,k] = sum_n dR[e,n] W[n,k]
@@ -587,17 +588,15 @@ void pairconv_bwd_dh(torch::Tensor Gt, torch::Tensor Ut, torch::Tensor Wt,
     const int PS = 4, PE = 128;
     int panels = ((eblk + PE - 1) / PE) * ((nsplit + PS - 1) / PS);
     dim3 grid((long)panels * PS * PE);
-    DISPATCH_O(O, {
+    DISPATCH_ORDER(O, kO, "O", {
         constexpr int LP = (kO == 1) ? 8 : opad_of(kO);
         size_t lds = 32768 + (size_t)(32 + 8) * 64 * LP * 2;   // dr | u[32][64][LP] | g[8][64][LP]
         hipLaunchKernelGGL(HIP_KERNEL_NAME(pairconv_bwd_dh_kernel<kO>), grid, dim3(NT), lds, stream,
-                           reinterpret_cast<const __bf16*>(Gt.data_ptr()),
-                           reinterpret_cast<const __bf16*>(Ut.data_ptr()),
-                           reinterpret_cast<const __bf16*>(Wt.data_ptr()),
+                           tptr<const __bf16>(Gt), tptr<const __bf16>(Ut),
+                           tptr<const __bf16>(Wt),
                            dH.data_ptr<float>(), E, mo, miF, nsplit, eblk);
     });
-    hipError_t err = hipGetLastError();
-    TORCH_CHECK(err == hipSuccess, "bwd_dh: ", hipGetErrorString(err));
+    check_launch("bwd_dh: ");
 }
 
 template <int O>
@@ -626,13 +625,10 @@ void pairconv_bwd_dw(torch::Tensor Gt, torch::Tensor Ut, torch::Tensor Ht,
     TORCH_CHECK(mo % 4 == 0 && miF % 32 == 0);
     auto stream = at::cuda::getCurrentHIPStream();
     dim3 grid((mo / 4) * (miF / 32));
-    DISPATCH_O(O, launch_dw<kO>(grid, stream,
-                                reinterpret_cast<const __bf16*>(Gt.data_ptr()),
-                                reinterpret_cast<const __bf16*>(Ut.data_ptr()),
-                                reinterpret_cast<const __bf16*>(Ht.data_ptr()),
-                                dW.data_ptr<float>(), E, mo, miF));
-    hipError_t err = hipGetLastError();
-    TORCH_CHECK(err == hipSuccess, "bwd_dw: ", hipGetErrorString(err));
+    DISPATCH_ORDER(O, kO, "O", launch_dw<kO>(
+        grid, stream, tptr<const __bf16>(Gt), tptr<const __bf16>(Ut),
+        tptr<const __bf16>(Ht), dW.data_ptr<float>(), E, mo, miF));
+    check_launch("bwd_dw: ");
 }
 
 void pairconv_bwd_du(torch::Tensor H, torch::Tensor W, torch::Tensor bias,
@@ -650,17 +646,14 @@ void pairconv_bwd_du(torch::Tensor H, torch::Tensor W, torch::Tensor bias,
     int ncb = miF / 32;
     int coh = (ncb % 8 == 0) ? 1 : 0;
     dim3 grid(nmemb * ncb);
-    DISPATCH_O(O, {
+    DISPATCH_ORDER(O, kO, "O", {
         size_t lds = 49152 + (size_t)((8 * kO * 64 * 2 + 15) & ~15) +
                      (size_t)32 * kO * 64 * 4 + 256 * 4;
         hipLaunchKernelGGL(HIP_KERNEL_NAME(pairconv_bwd_du_kernel<kO>),
                            grid, dim3(NT), lds, stream,
-                           reinterpret_cast<const __bf16*>(H.data_ptr()),
-                           reinterpret_cast<const __bf16*>(W.data_ptr()),
-                           bias.data_ptr<float>(),
-                           reinterpret_cast<const __bf16*>(Gt.data_ptr()),
+                           tptr<const __bf16>(H), tptr<const __bf16>(W),
+                           bias.data_ptr<float>(), tptr<const __bf16>(Gt),
                            dU.data_ptr<float>(), E, mo, miF, nmemb, coh);
     });
-    hipError_t err = hipGetLastError();
-    TORCH_CHECK(err == hipSuccess, "bwd_du: ", hipGetErrorString(err));
+    check_launch("bwd_du: ");
 }

@@ -3,9 +3,7 @@
 // them; what only one kernel needs stays next to that kernel.
 #pragma once
 
-#include <torch/extension.h>
-#include <hip/hip_runtime.h>
-#include <ATen/hip/HIPContext.h>
+#include "host_common.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
@@ -21,8 +19,8 @@ typedef __attribute__((ext_vector_type(2))) float f32x2;
 // Padded o width OP(O) of the edge-major tensors U (miF, E, OP) bf16,
 // G (mo, E, OP) bf16 and dU (miF, E, OP) f32: all o of one (row, edge) are
 // one aligned vector, and the pad lanes o in [O, OP) are exactly zero, so a
-// consumer contracts whole vectors. The one definition; Python reads it
-// through pairconv_opad().
+// consumer contracts whole vectors. The one definition; ops/fused.py mirrors
+// it and checks pairconv_opad() at load.
 __host__ __device__ constexpr int opad_of(int O) {
     return O == 1 ? 1 : (O <= 3 ? 4 : 8);
 }
@@ -158,12 +156,3 @@ __device__ __forceinline__ void cohort_map(int coh, int nmemb, int& eb, int& grp
         grp = blockIdx.x / nmemb;
     }
 }
-
-#define DISPATCH_O(O, ...)                                         \
-    switch (O) {                                                   \
-        case 1: { constexpr int kO = 1; __VA_ARGS__; break; }      \
-        case 3: { constexpr int kO = 3; __VA_ARGS__; break; }      \
-        case 5: { constexpr int kO = 5; __VA_ARGS__; break; }      \
-        case 7: { constexpr int kO = 7; __VA_ARGS__; break; }      \
-        default: TORCH_CHECK(false, "unsupported O ", O);          \
-    }

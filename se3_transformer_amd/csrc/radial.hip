@@ -21,9 +21,9 @@
 // all the pair's edge blocks, so LDS is spent on the per-edge tiles
 // instead (keeps 4 blocks/CU).
 
-#include <torch/extension.h>
 #include <hip/hip_runtime.h>
-#include <ATen/hip/HIPContext.h>
+#include "host_common.h"
+#include "ops.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -433,18 +433,13 @@ void radial_trunk_fwd(torch::Tensor X, torch::Tensor W0, torch::Tensor p0,
         size_t lds = RT_E * 256 + RT_E * RT_PITCH * 4 + RT_E * kD * 4;
         hipLaunchKernelGGL(HIP_KERNEL_NAME(radial_trunk_fwd_kernel<kD>),
                            grid, dim3(RT_NT), lds, stream,
-                           reinterpret_cast<const __bf16*>(X.data_ptr()),
-                           reinterpret_cast<const __bf16*>(W0.data_ptr()),
-                           p0.data_ptr<float>(),
-                           reinterpret_cast<const __bf16*>(W3.data_ptr()),
-                           p3.data_ptr<float>(),
-                           reinterpret_cast<__bf16*>(H.data_ptr()),
-                           reinterpret_cast<__bf16*>(yh0.data_ptr()),
-                           reinterpret_cast<__bf16*>(yh3.data_ptr()),
+                           tptr<const __bf16>(X), tptr<const __bf16>(W0),
+                           p0.data_ptr<float>(), tptr<const __bf16>(W3),
+                           p3.data_ptr<float>(), tptr<__bf16>(H),
+                           tptr<__bf16>(yh0), tptr<__bf16>(yh3),
                            rs01.data_ptr<float>(), E, (float)eps);
     });
-    hipError_t err = hipGetLastError();
-    TORCH_CHECK(err == hipSuccess, "radial_trunk_fwd: ", hipGetErrorString(err));
+    check_launch("radial_trunk_fwd: ");
 }
 
 void radial_trunk_bwd(torch::Tensor dH, torch::Tensor X, torch::Tensor W0,
@@ -458,41 +453,22 @@ void radial_trunk_bwd(torch::Tensor dH, torch::Tensor X, torch::Tensor W0,
     bool needx = dX.defined() && dX.numel() > 0;
     auto stream = at::cuda::getCurrentHIPStream();
     dim3 grid((E + RT_E - 1) / RT_E);
+#define RT_LAUNCH_BWD(NX, DX)                                                   \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(radial_trunk_bwd_kernel<kD, NX>),        \
+                       grid, dim3(RT_NT), lds, stream,                          \
+                       tptr<const __bf16>(dH), tptr<const __bf16>(X),           \
+                       tptr<const __bf16>(W0), p0.data_ptr<float>(),            \
+                       tptr<const __bf16>(W3), tptr<const __bf16>(W3t),         \
+                       p3.data_ptr<float>(),                                    \
+                       tptr<const __bf16>(yh0), tptr<const __bf16>(yh3),        \
+                       rs01.data_ptr<float>(), dW0.data_ptr<float>(),           \
+                       dp0.data_ptr<float>(), dW3.data_ptr<float>(),            \
+                       dp3.data_ptr<float>(), DX, E, (float)eps)
     RT_DISPATCH_D(D, {
         size_t lds = 32768 + 2 * RT_E * RT_PITCH * 4 + 4 * RT_K * 4 + RT_E * kD * 4;
-        if (needx) {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(radial_trunk_bwd_kernel<kD, 1>),
-                               grid, dim3(RT_NT), lds, stream,
-                               reinterpret_cast<const __bf16*>(dH.data_ptr()),
-                               reinterpret_cast<const __bf16*>(X.data_ptr()),
-                               reinterpret_cast<const __bf16*>(W0.data_ptr()),
-                               p0.data_ptr<float>(),
-                               reinterpret_cast<const __bf16*>(W3.data_ptr()),
-                               reinterpret_cast<const __bf16*>(W3t.data_ptr()),
-                               p3.data_ptr<float>(),
-                               reinterpret_cast<const __bf16*>(yh0.data_ptr()),
-                               reinterpret_cast<const __bf16*>(yh3.data_ptr()),
-                               rs01.data_ptr<float>(), dW0.data_ptr<float>(),
-                               dp0.data_ptr<float>(), dW3.data_ptr<float>(),
-                               dp3.data_ptr<float>(), dX.data_ptr<float>(),
-                               E, (float)eps);
-        } else {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(radial_trunk_bwd_kernel<kD, 0>),
-                               grid, dim3(RT_NT), lds, stream,
-                               reinterpret_cast<const __bf16*>(dH.data_ptr()),
-                               reinterpret_cast<const __bf16*>(X.data_ptr()),
-                               reinterpret_cast<const __bf16*>(W0.data_ptr()),
-                               p0.data_ptr<float>(),
-                               reinterpret_cast<const __bf16*>(W3.data_ptr()),
-                               reinterpret_cast<const __bf16*>(W3t.data_ptr()),
-                               p3.data_ptr<float>(),
-                               reinterpret_cast<const __bf16*>(yh0.data_ptr()),
-                               reinterpret_cast<const __bf16*>(yh3.data_ptr()),
-                               rs01.data_ptr<float>(), dW0.data_ptr<float>(),
-                               dp0.data_ptr<float>(), dW3.data_ptr<float>(),
-                               dp3.data_ptr<float>(), nullptr, E, (float)eps);
-        }
+        if (needx) RT_LAUNCH_BWD(1, dX.data_ptr<float>());
+        else RT_LAUNCH_BWD(0, nullptr);
     });
-    hipError_t err = hipGetLastError();
-    TORCH_CHECK(err == hipSuccess, "radial_trunk_bwd: ", hipGetErrorString(err));
+#undef RT_LAUNCH_BWD
+    check_launch("radial_trunk_bwd: ");
 }

@@ -15,9 +15,9 @@
 // the same LDS column now holding dY; the per-edge math is sh_basis_bwd.h.
 // Each edge owns its row, so there are no atomics.
 
-#include <torch/extension.h>
 #include <hip/hip_runtime.h>
-#include <ATen/hip/HIPContext.h>
+#include "host_common.h"
+#include "ops.h"
 
 #include "sh_basis_bwd.h"
 
@@ -119,8 +119,7 @@ void sh_basis_fwd(torch::Tensor rel, torch::Tensor qcat, torch::Tensor normtab,
                        normtab.data_ptr<float>(),
                        reinterpret_cast<const int4*>(meta.data_ptr<int>()),
                        npairs, out.data_ptr<float>(), E, TOT, (int)L);
-    hipError_t err = hipGetLastError();
-    TORCH_CHECK(err == hipSuccess, "sh_basis: ", hipGetErrorString(err));
+    check_launch("sh_basis: ");
 }
 
 __global__ void __launch_bounds__(NTSH)
@@ -168,6 +167,5 @@ void sh_basis_bwd(torch::Tensor rel, torch::Tensor qcat, torch::Tensor normtab,
                        normtab.data_ptr<float>(), meta.data_ptr<int>(),
                        npairs, dK.data_ptr<float>(), drel.data_ptr<float>(),
                        E, TOT, (int)L);
-    hipError_t err = hipGetLastError();
-    TORCH_CHECK(err == hipSuccess, "sh_basis_bwd: ", hipGetErrorString(err));
+    check_launch("sh_basis_bwd: ");
 }

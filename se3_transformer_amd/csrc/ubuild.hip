@@ -23,9 +23,9 @@
 // holds B and a dU tile, and adding the fp32 dB tile would pass 64 KiB for
 // the (7,7,7) pair. The price is one extra read of dU on that path only.
 
-#include <torch/extension.h>
 #include <hip/hip_runtime.h>
-#include <ATen/hip/HIPContext.h>
+#include "host_common.h"
+#include "ops.h"
 #include "pairconv_common.h"
 
 #define UB_NT 256
@@ -262,27 +262,18 @@ void ubuild_fwd(torch::Tensor B, torch::Tensor X, torch::Tensor Ut,
     auto stream = at::cuda::getCurrentHIPStream();
     dim3 grid((E + UB_E - 1) / UB_E);
     size_t lds = (size_t)UB_E * O * F * 8 * 2 + (size_t)UB_C * UB_E * 8 * 2;
-#define UB_LAUNCH_FWD(TX, XPTR, OPV)                                          \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(ubuild_fwd_kernel<TX, OPV>), grid,        \
-                       dim3(UB_NT), lds, stream, B.data_ptr<float>(), XPTR,      \
-                       reinterpret_cast<__bf16*>(Ut.data_ptr()),                 \
+#define UB_LAUNCH_FWD(OPV)                                                    \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(ubuild_fwd_kernel<T, OPV>), grid,      \
+                       dim3(UB_NT), lds, stream, B.data_ptr<float>(),         \
+                       tptr<const T>(X), tptr<__bf16>(Ut),                    \
                        E, C, (int)O, (int)I, (int)F)
-#define UB_LAUNCH_FWD_OP(TX, XPTR)                                               \
-    do {                                                                         \
-        if (OP == 8) UB_LAUNCH_FWD(TX, XPTR, 8);                                 \
-        else if (OP == 4) UB_LAUNCH_FWD(TX, XPTR, 4);                            \
-        else UB_LAUNCH_FWD(TX, XPTR, 1);                                         \
-    } while (0)
-    if (X.dtype() == torch::kFloat32) {
-        UB_LAUNCH_FWD_OP(float, X.data_ptr<float>());
-    } else {
-        TORCH_CHECK(X.dtype() == torch::kBFloat16);
-        UB_LAUNCH_FWD_OP(__bf16, reinterpret_cast<const __bf16*>(X.data_ptr()));
-    }
-#undef UB_LAUNCH_FWD_OP
+    DISPATCH_F32_BF16(X, __bf16, {
+        if (OP == 8) UB_LAUNCH_FWD(8);
+        else if (OP == 4) UB_LAUNCH_FWD(4);
+        else UB_LAUNCH_FWD(1);
+    });
 #undef UB_LAUNCH_FWD
-    hipError_t err = hipGetLastError();
-    TORCH_CHECK(err == hipSuccess, "ubuild_fwd: ", hipGetErrorString(err));
+    check_launch("ubuild_fwd: ");
 }
 
 void ubuild_bwd_dx(torch::Tensor B, torch::Tensor dU, torch::Tensor dX,
@@ -300,21 +291,13 @@ void ubuild_bwd_dx(torch::Tensor B, torch::Tensor dU, torch::Tensor dX,
     auto stream = at::cuda::getCurrentHIPStream();
     dim3 grid((E + UB_EB - 1) / UB_EB);
     size_t lds = (size_t)UB_EB * O * I * F * 4 + (size_t)UB_CB * F * O * UB_EB * 4;
-    if (dX.dtype() == torch::kFloat32) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(ubuild_bwd_dx_kernel<float>), grid,
+    DISPATCH_F32_BF16(dX, __bf16, {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(ubuild_bwd_dx_kernel<T>), grid,
                            dim3(UB_NT), lds, stream, B.data_ptr<float>(),
-                           dU.data_ptr<float>(), dX.data_ptr<float>(),
+                           dU.data_ptr<float>(), tptr<T>(dX),
                            E, C, (int)O, (int)I, (int)F);
-    } else {
-        TORCH_CHECK(dX.dtype() == torch::kBFloat16);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(ubuild_bwd_dx_kernel<__bf16>), grid,
-                           dim3(UB_NT), lds, stream, B.data_ptr<float>(),
-                           dU.data_ptr<float>(),
-                           reinterpret_cast<__bf16*>(dX.data_ptr()),
-                           E, C, (int)O, (int)I, (int)F);
-    }
-    hipError_t err = hipGetLastError();
-    TORCH_CHECK(err == hipSuccess, "ubuild_bwd_dx: ", hipGetErrorString(err));
+    });
+    check_launch("ubuild_bwd_dx: ");
 }
 
 void ubuild_bwd_db(torch::Tensor X, torch::Tensor dU, torch::Tensor dB,
@@ -337,19 +320,11 @@ void ubuild_bwd_db(torch::Tensor X, torch::Tensor dU, torch::Tensor dB,
     TORCH_CHECK(lds <= 64 * 1024, "degree pair too large for LDS staging");
     auto stream = at::cuda::getCurrentHIPStream();
     dim3 grid((E + UB_EB - 1) / UB_EB);
-    if (X.dtype() == torch::kFloat32) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(ubuild_bwd_db_kernel<float>), grid,
-                           dim3(UB_NT), lds, stream, X.data_ptr<float>(),
+    DISPATCH_F32_BF16(X, __bf16, {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(ubuild_bwd_db_kernel<T>), grid,
+                           dim3(UB_NT), lds, stream, tptr<const T>(X),
                            dU.data_ptr<float>(), dB.data_ptr<float>(),
                            E, C, (int)O, (int)I, (int)F);
-    } else {
-        TORCH_CHECK(X.dtype() == torch::kBFloat16);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(ubuild_bwd_db_kernel<__bf16>), grid,
-                           dim3(UB_NT), lds, stream,
-                           reinterpret_cast<const __bf16*>(X.data_ptr()),
-                           dU.data_ptr<float>(), dB.data_ptr<float>(),
-                           E, C, (int)O, (int)I, (int)F);
-    }
-    hipError_t err = hipGetLastError();
-    TORCH_CHECK(err == hipSuccess, "ubuild_bwd_db: ", hipGetErrorString(err));
+    });
+    check_launch("ubuild_bwd_db: ");
 }

@@ -7,12 +7,12 @@ neighbor-attention kernel on GPU; the einsum path below is the oracle.
 """
 from __future__ import annotations
 
-import os
-
 import torch
 import torch.nn.functional as F
 from torch import nn
 
+from ..ops import fused as _fused
+from ..ops.fused import attn_ok as _attn_kernel_ok, rope_ok as _rope_in_kernel_ok
 from ..utils import batched_index_select, map_values, to_order
 from .core import ConvSE3, LinearSE3, NormSE3, ResidualSE3
 from .fiber import Fiber
@@ -31,38 +31,6 @@ def apply_rotary_pos_emb(t, freqs):
     half_rot = torch.cat((-odd, even), dim=-2)
     t_rot = t_rot * freqs.cos() + half_rot * freqs.sin()
     return torch.cat((t_rot, t_pass), dim=-2)
-
-
-def _first_tensor(features):
-    return next(iter(features.values()))
-
-
-def _attn_kernel_ok(q, J, dm):
-    """Gate for the fused HIP attention kernel (csrc/attn2.hip): any J via
-    online-softmax tiles; DM bounded by the per-lane register chunking."""
-    from ..ops import fused as _fused
-    max_j = int(os.environ.get('SE3_ATTN_MAX_J', 100000))
-    return (q.is_cuda and J <= max_j and dm <= 448
-            and q.dtype in (torch.float32, torch.bfloat16)
-            and os.environ.get('SE3_EAGER_ATTN') != '1'
-            and _fused.ext_available())
-
-
-def _rope_in_kernel_ok(q, j_pre, qpe, kpe, use_null_kv, global_feats):
-    """True if the rotary embedding can be folded into the attention kernel
-    (q/k/v rotated in-registers) instead of materializing rotated copies.
-    The frequency tables must not need grad (rotary_rel_dist with
-    differentiable coordinates falls back to the eager path)."""
-    rot = qpe.shape[-1]
-    gj = 0
-    if global_feats is not None:   # fiber dict {'0': (b, gj, d, 1)}
-        gj = _first_tensor(global_feats).shape[1]
-    j_fin = j_pre + (1 if use_null_kv else 0) + gj
-    dm = q.shape[-2] * q.shape[-1]
-    return (_attn_kernel_ok(q, j_fin, dm)
-            and rot <= 64 and rot % 2 == 0 and rot <= dm
-            and kpe.shape[2] == j_pre
-            and not qpe.requires_grad and not kpe.requires_grad)
 
 
 class AttentionSE3(nn.Module):
@@ -202,7 +170,6 @@ class AttentionSE3(nn.Module):
 
             bq, hq, nq, dq, mq = q.shape
             J = k.shape[3]
-            from ..ops import fused as _fused
             if _attn_kernel_ok(q, J, dq * mq) or rope_q is not None:
                 mask_u8 = None
                 if neighbor_mask is not None:
@@ -360,7 +327,6 @@ class OneHeadedKVAttentionSE3(nn.Module):
 
             bq, hq, nq, dq, mq = q.shape
             J = k.shape[2]
-            from ..ops import fused as _fused
             if _attn_kernel_ok(q, J, dq * mq) or rope_q is not None:
                 mask_u8 = None
                 if neighbor_mask is not None:

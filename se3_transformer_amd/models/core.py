@@ -15,7 +15,6 @@ distributions match. The COMPUTE is restructured MI355X-first:
 """
 from __future__ import annotations
 
-import os
 from math import sqrt
 
 import torch
@@ -108,8 +107,6 @@ class NormSE3(nn.Module):
 
     def _fused_nonlin(self):
         """Name of the kernels' nonlinearity selector, or None for eager."""
-        if os.environ.get('SE3_EAGER_NORM') == '1':
-            return None
         if isinstance(self.nonlin, nn.Identity):
             return 'identity'
         if (isinstance(self.nonlin, nn.GELU)
@@ -117,27 +114,13 @@ class NormSE3(nn.Module):
             return 'gelu'
         return None
 
-    @staticmethod
-    def _fused_ok(t, gated, nonlin):
-        from ..ops import fused
-        if not (nonlin is not None and t.is_cuda and t.dim() >= 2
-                and t.shape[-1] in (1, 3, 5, 7)
-                and t.dtype in (torch.float32, torch.bfloat16)
-                and fused.ext_available()):
-            return False
-        if gated and t.shape[-2] > fused.NORM_GATED_MAX_C:
-            return False    # LDS tile of the gated kernels: eager above it
-        # scale+GELU is the original kernel pair; the rest need the newer
-        # entry points, and a build without them raises
-        return (not gated and nonlin == 'gelu') or fused.norm_variants_ok()
-
     def forward(self, features):
         from ..ops import fused
         nonlin = self._fused_nonlin()
         output = {}
         for degree, t in features.items():
             params = self.transform[degree]
-            if self._fused_ok(t, 'w_gate' in params, nonlin):
+            if fused.norm_ok(t, 'w_gate' in params, nonlin):
                 if 'scale' in params:
                     output[degree] = fused.norm_se3(
                         t.contiguous(), params['scale'], self.eps, nonlin)
@@ -197,8 +180,7 @@ class RadialFunc(nn.Module):
         HIP kernel each way (csrc/radial.hip); eager fallback otherwise."""
         from ..ops import fused as _fused
         in_dim = x.shape[-1]
-        if (x.is_cuda and os.environ.get('SE3_EAGER_RADIAL') != '1'
-                and _fused.radial_trunk_ok(in_dim, self.mid_dim)):
+        if _fused.radial_ok(x, self.mid_dim):
             n0, ln1 = self.net[0], self.net[1]
             n3, ln4 = self.net[3], self.net[4]
             lead = x.shape[:-1]
@@ -268,18 +250,12 @@ class PairwiseConv(nn.Module):
 
         # MI355X fused HIP path: bf16 compute on CUDA(ROCm) devices
         from ..ops import fused as _fused
-        want_bf16 = (torch.is_autocast_enabled()
-                     or xg.dtype == torch.bfloat16
-                     or os.environ.get('SE3_FORCE_FUSED') == '1')
-        if (xg.is_cuda and want_bf16
-                and _fused.fused_shapes_ok(mo, mi * F_, O, self.rp.mid_dim)):
-            _fused.require_ext()
+        if _fused.pairconv_ok(xg, mo, mi * F_, O, self.rp.mid_dim):
             h = self.rp.hidden(ef)                           # (E, 128)
             # u[(mi,f), e, o] = sum_i B[e,o,i,f] x[e,mi,i], written once in
             # the o-padded layout every pairconv kernel reads
             w6 = self.rp.net[6]
-            if (_fused.ubuild_ok(braw, mi, O, I, F_)
-                    and os.environ.get('SE3_EAGER_UBUILD') != '1'):
+            if _fused.ubuild_ok(braw, mi, O, I, F_):
                 u = _fused.ubuild_opad(xg, braw.contiguous(), O, I, F_)
                 out = _fused.fused_pairconv_opad(h, w6.weight, w6.bias, u,
                                                  mo, O)
@@ -371,13 +347,11 @@ class ConvSE3(nn.Module):
             gathered[di] = x  # (b, n, k, mi, 2di+1)
 
         pairs = list(self.fiber_in * self.fiber_out)
-        # opt-in: overlaps independent pairs on a stream pool, but is NOT
-        # compatible with hipGraph step capture (capture with forked streams
-        # hangs on ROCm 7.2) — default off
+        # opt-in: overlaps independent pairs on a stream pool; capture with
+        # forked streams hangs on ROCm 7.2, so single-stream loop mid-capture
+        from ..ops.fused import switch_on
         use_streams = (edge_feats.is_cuda and len(pairs) > 1
-                       and os.environ.get('SE3_STREAMS') == '1'
-                       # forked streams hang under hipGraph capture on ROCm
-                       # 7.2: fall back to the single-stream loop mid-capture
+                       and switch_on('SE3_STREAMS')
                        and not torch.cuda.is_current_stream_capturing())
 
         pair_out = {}

@@ -82,8 +82,7 @@ class EGNN(nn.Module):
         # the EGNN trunk usable at n ~ 1024.
         from ..ops import fused as _fused
         max_m = max((t.shape[-1] for _, t in htypes), default=0)
-        use_kernels = (nodes.is_cuda and len(htypes) > 0
-                       and _fused.egnn_kernels_ok(max_m))
+        use_kernels = _fused.egnn_ok(nodes, len(htypes), max_m)
 
         rel_htypes = []
         if use_kernels:

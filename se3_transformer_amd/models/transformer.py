@@ -7,7 +7,6 @@ masked_select) graph construction, fused conv path, no `splits` chunking.
 """
 from __future__ import annotations
 
-import os
 
 import torch
 import torch.nn.functional as F
@@ -321,10 +320,7 @@ class SE3Transformer(nn.Module):
         # budget stay on the eager branch.
         from ..ops import fused as _fusedmod
         k_total = int(min(neighbors + num_sparse_neighbors, n - 1))  # neighbors may be inf
-        use_knn = (coors.is_cuda and coors.dtype == torch.float32
-                   and _fusedmod.knn_ok(n, k_total)
-                   and os.environ.get('SE3_EAGER_KNN') != '1'
-                   and _fusedmod.ext_available())
+        use_knn = _fusedmod.knn_kernel_ok(coors, n, k_total)
 
         if use_knn:
             k_eff = k_total
@@ -350,7 +346,7 @@ class SE3Transformer(nn.Module):
                                 dist, relp, nm, k_eff,
                                 radius, bool(self.causal))
 
-            if os.environ.get('SE3_COMPACT_NEIGHBORS') == '1' \
+            if _fusedmod.switch_on('SE3_COMPACT_NEIGHBORS') \
                     and not torch.cuda.is_current_stream_capturing():
                 # each row comes out in ascending distance, so with a
                 # radius (or a causal / thinned row) the valid slots sit at

@@ -249,31 +249,6 @@ def _build_sh_tables(key, max_degree, device):
     return tables
 
 
-class _ShBasisFn(torch.autograd.Function):
-    """Fused SH + basis kernel with its HIP backward (csrc/sh_basis.hip):
-    rel (E,3) fp32 -> packed basis (E,TOT) fp32, and dK -> d rel. First order
-    only; second-order gradients need the eager path (SE3_EAGER_BASIS=1)."""
-
-    @staticmethod
-    def forward(ctx, rel, qcat, normtab, meta, TOT, L):
-        from . import fused as _fused
-        out = torch.empty(rel.shape[0], TOT, dtype=torch.float32, device=rel.device)
-        _fused._EXT.sh_basis_fwd(rel, qcat, normtab, meta, out, L)
-        ctx.save_for_backward(rel, qcat, normtab, meta)
-        ctx.L = L
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dK):
-        from . import fused as _fused
-        rel, qcat, normtab, meta = ctx.saved_tensors
-        drel = torch.empty_like(rel)
-        _fused._EXT.sh_basis_bwd(rel, qcat, normtab, meta,
-                                 dK.contiguous().float(), drel, ctx.L)
-        return drel, None, None, None, None, None
-
-
 def get_basis_packed(r_ij: torch.Tensor, max_degree: int, differentiable: bool = False):
     """Compact per-pair basis for the fused conv path.
 
@@ -289,28 +264,19 @@ def get_basis_packed(r_ij: torch.Tensor, max_degree: int, differentiable: bool =
     """
     device, dtype = r_ij.device, r_ij.dtype
 
-    if (r_ij.is_cuda and dtype == torch.float32
-            and os.environ.get('SE3_EAGER_BASIS') != '1'):
-        from . import fused as _fused
-        if _fused.ext_available():
-            qcat, normtab, meta, TOT, layout = _sh_basis_tables(max_degree, device)
-            rel = r_ij.reshape(-1, 3).contiguous()
-            E = rel.shape[0]
-            if differentiable and rel.requires_grad and torch.is_grad_enabled():
-                out = _ShBasisFn.apply(rel, qcat, normtab, meta, TOT,
-                                       2 * max_degree)
-            else:
-                out = torch.empty(E, TOT, dtype=torch.float32, device=device)
-                _fused._EXT.sh_basis_fwd(rel.detach(), qcat, normtab, meta,
-                                         out, 2 * max_degree)
-            # layout offsets are consecutive: one split (a single cat in
-            # backward) instead of per-pair slices (one padded E x TOT
-            # gradient each)
-            parts = out.split([O * I * F for _, O, I, F in layout.values()], dim=1)
-            basis = {}
-            for (pair, (off, O, I, F)), part in zip(layout.items(), parts):
-                basis[pair] = part.reshape(*r_ij.shape[:-1], O, I, F)
-            return basis
+    from . import fused as _fused
+    if _fused.sh_basis_ok(r_ij):
+        qcat, normtab, meta, TOT, layout = _sh_basis_tables(max_degree, device)
+        out = _fused.sh_basis(r_ij.reshape(-1, 3).contiguous(), qcat, normtab,
+                              meta, TOT, 2 * max_degree, differentiable)
+        # layout offsets are consecutive: one split (a single cat in
+        # backward) instead of per-pair slices (one padded E x TOT
+        # gradient each)
+        parts = out.split([O * I * F for _, O, I, F in layout.values()], dim=1)
+        basis = {}
+        for (pair, (off, O, I, F)), part in zip(layout.items(), parts):
+            basis[pair] = part.reshape(*r_ij.shape[:-1], O, I, F)
+        return basis
     y_packed = _compute_sh(r_ij, 2 * max_degree, differentiable)
 
     basis = {}

@@ -1,19 +1,59 @@
 """Fused-kernel dispatch layer (MI355X HIP extension, se3_transformer_amd._C).
 
-Autograd Functions wrapping the hand-written CDNA4 kernels in csrc/:
-pairwise convolution (fwd + the three dedicated backward kernels + the
-one-pass dual-layout weight pack — the per-edge radial output R of
-reference se3_transformer_pytorch.py:297-343 never touches HBM in either
-direction), the radial trunk, the basis×features precontraction, NormSE3,
-neighbor attention v2 (online softmax, in-kernel rotary, HIP backward)
-and the EGNN higher-type ops. A chunked library-GEMM backward for the
-pairconv remains behind SE3_TORCH_BWD as the parity oracle.
+This module alone decides kernel vs eager. SWITCHES lists the runtime SE3_*
+switches and switch() reads one, at call time. Each kernel family has one
+gate (norm_ok ... egnn_ok) over shape arithmetic that needs no extension
+(fused_shapes_ok, knn_ok, attn_shapes_ok, norm_shapes_ok). A gate tests
+device, dtype, shape and switch before it touches the extension, so a CPU
+forward never imports _C. Without the extension on a GPU pairconv_ok raises
+and every other gate answers False (eager). _load_ext() checks the entry
+points and the constants mirrored here once, at load.
+
+Below them sit the autograd Functions wrapping the hand-written CDNA4
+kernels in csrc/: pairwise convolution (fwd + the three dedicated backward
+kernels + the one-pass dual-layout weight pack — the per-edge radial output
+R of reference se3_transformer_pytorch.py:297-343 never touches HBM in
+either direction), the radial trunk, the basis×features precontraction, the
+SH basis, NormSE3, neighbor attention v2 (online softmax, in-kernel rotary,
+HIP backward) and the EGNN higher-type ops. A chunked library-GEMM backward
+for the pairconv remains behind SE3_TORCH_BWD as the parity oracle.
 """
 from __future__ import annotations
 
 import os
 
 import torch
+
+# Every runtime switch (the README table lists the same names). All are
+# on/off, on when set to '1', except SE3_ATTN_MAX_J, which holds a number.
+SWITCHES = {
+    'SE3_EAGER_NORM': 'NormSE3 runs eager',
+    'SE3_EAGER_RADIAL': 'the radial trunk runs eager',
+    'SE3_EAGER_UBUILD': 'the basis x features precontraction runs eager',
+    'SE3_EAGER_ATTN': 'neighbor attention (and its rotary) runs eager',
+    'SE3_EAGER_KNN': 'the neighbor graph is built eager',
+    'SE3_EAGER_BASIS': 'the SH basis runs eager',
+    'SE3_EAGER_EGNN': 'the EGNN higher-type ops run eager',
+    'SE3_FORCE_FUSED': 'pairconv kernels also for fp32 input outside autocast',
+    'SE3_TORCH_BWD': 'pairconv backward through library GEMMs (parity oracle)',
+    'SE3_LOWMEM_PACK': 'save W unpacked and re-pack in the pairconv backward',
+    'SE3_COMPACT_NEIGHBORS': 'cut neighbor columns that are invalid in every row',
+    'SE3_STREAMS': 'run the degree pairs of a ConvSE3 on a stream pool',
+    'SE3_ATTN_MAX_J': 'largest neighbor count the attention kernel takes',
+}
+
+
+def switch(name: str):
+    """The environment's value of a runtime switch, read now: tests and
+    scripts flip switches inside a process, so nothing is cached."""
+    if name not in SWITCHES:
+        raise KeyError(name)
+    return os.environ.get(name)
+
+
+def switch_on(name: str) -> bool:
+    return switch(name) == '1'
+
 
 _EXT = None
 _EXT_ERR = None
@@ -22,16 +62,14 @@ _EXT_ERR = None
 # caller probes the module again: a stale build is an error at load, not a
 # reason to run eager.
 _ENTRY_POINTS = (
-    'pairconv_fwd', 'pairconv_fwd_opad', 'pairconv_opad',
-    'pairconv_bwd_dh', 'pairconv_bwd_dw', 'pairconv_bwd_du',
-    'pack_w_both', 'pack_g', 'radial_trunk_fwd', 'radial_trunk_bwd',
-    'ubuild_fwd', 'ubuild_bwd_dx', 'ubuild_bwd_db',
+    'pairconv_fwd_opad', 'pairconv_opad', 'pairconv_bwd_dh', 'pairconv_bwd_dw',
+    'pairconv_bwd_du', 'pack_w_both', 'pack_g', 'radial_trunk_fwd',
+    'radial_trunk_bwd', 'ubuild_fwd', 'ubuild_bwd_dx', 'ubuild_bwd_db',
     'sh_basis_fwd', 'sh_basis_bwd', 'knn_graph', 'knn_max_lds_bytes',
-    'attn2_fwd', 'attn2_bwd',
-    'norm_se3_nl_fwd', 'norm_se3_nl_bwd', 'norm_se3_gated_max_c',
-    'norm_se3_gated_fwd', 'norm_se3_gated_bwd',
-    'egnn_rel_dist_fwd', 'egnn_rel_dist_bwd',
-    'egnn_htype_update_fwd', 'egnn_htype_update_bwd',
+    'attn2_fwd', 'attn2_bwd', 'norm_se3_nl_fwd', 'norm_se3_nl_bwd',
+    'norm_se3_gated_max_c', 'norm_se3_gated_fwd', 'norm_se3_gated_bwd',
+    'egnn_rel_dist_fwd', 'egnn_rel_dist_bwd', 'egnn_htype_update_fwd',
+    'egnn_htype_update_bwd',
 )
 
 # Channel ceiling of the gated kernels (GATED_MAX_C in csrc/norm_se3.hip):
@@ -43,7 +81,10 @@ NORM_GATED_MAX_C = 2048
 # holds 64 sorted lists of L = min(k, ceil(n/64)) (distance, index) pairs
 # plus the k winners.
 KNN_MAX_LDS = 65536
-_KNN_BUDGET_CHECKED = False
+
+# Padded o width OP(O) of the edge-major tensors U (miF, E, OP),
+# G (mo, E, OP) and dU (miF, E, OP) (opad_of in csrc/pairconv_common.h).
+_OPAD = {1: 1, 3: 4, 5: 8, 7: 8}
 
 
 def _load_ext():
@@ -55,8 +96,13 @@ def _load_ext():
             _EXT_ERR = e
             return None
         missing = [n for n in _ENTRY_POINTS if not hasattr(mod, n)]
-        if not missing and mod.norm_se3_gated_max_c() != NORM_GATED_MAX_C:
-            missing = [f'norm_se3_gated_max_c() == {NORM_GATED_MAX_C}']
+        if not missing:
+            if mod.norm_se3_gated_max_c() != NORM_GATED_MAX_C:
+                missing.append(f'norm_se3_gated_max_c() == {NORM_GATED_MAX_C}')
+            if mod.knn_max_lds_bytes() != KNN_MAX_LDS:
+                missing.append(f'knn_max_lds_bytes() == {KNN_MAX_LDS}')
+            missing += [f'pairconv_opad({O}) == {OP}' for O, OP in _OPAD.items()
+                        if mod.pairconv_opad(O) != OP]
         if missing:
             raise RuntimeError(
                 'se3_transformer_amd._C lacks ' + ', '.join(missing)
@@ -79,37 +125,112 @@ def require_ext():
             f'(import error: {_EXT_ERR})')
 
 
+# Shape arithmetic first (no extension needed to ask), then one gate per family.
+
 def knn_lds_bytes(n: int, k: int) -> int:
     return min(k, -(-n // 64)) * 64 * 8 + 4 * k
 
 
 def knn_ok(n: int, k: int) -> bool:
     """True when the kNN kernel serves (n, k): any 1 <= k <= n-1 whose LDS
-    footprint fits KNN_MAX_LDS (k = n-1 up to n ~ 5400). Pure Python, the
-    extension is not needed to ask."""
+    footprint fits KNN_MAX_LDS (k = n-1 up to n ~ 5400)."""
     return 1 <= k <= n - 1 and knn_lds_bytes(n, k) <= KNN_MAX_LDS
-
-
-def knn_graph(coors, nmask, allow, sparse, idx, dist, rel, m, k, radius,
-              causal):
-    """csrc/knn.hip. The first call checks KNN_MAX_LDS against the built
-    kernel's knn_max_lds_bytes(): knn_ok() must gate on the budget the
-    kernel enforces, so a stale build is an error, not a wrong gate."""
-    global _KNN_BUDGET_CHECKED
-    ext = _load_ext()
-    if not _KNN_BUDGET_CHECKED:
-        if ext.knn_max_lds_bytes() != KNN_MAX_LDS:
-            raise RuntimeError(
-                'se3_transformer_amd._C lacks knn_max_lds_bytes() == '
-                f'{KNN_MAX_LDS}; rebuild the extension '
-                '(python scripts/build_ext.py)')
-        _KNN_BUDGET_CHECKED = True
-    ext.knn_graph(coors, nmask, allow, sparse, idx, dist, rel, m, k, radius,
-                  causal)
 
 
 def fused_shapes_ok(mo: int, miF: int, O: int, mid_dim: int) -> bool:
     return mid_dim == 128 and miF % 32 == 0 and mo % 8 == 0 and O in (1, 3, 5, 7)
+
+
+def attn_shapes_ok(J: int, dm: int, rot: int = 0) -> bool:
+    """csrc/attn2.hip: any J up to SE3_ATTN_MAX_J, DM bounded by the per-lane
+    register chunking, in-kernel rotary width even, <= 64 and within DM."""
+    max_j = switch('SE3_ATTN_MAX_J')
+    return (J <= (100000 if max_j is None else int(max_j)) and dm <= 448
+            and rot <= 64 and rot % 2 == 0 and rot <= dm)
+
+
+def norm_shapes_ok(C: int, M: int, gated: bool) -> bool:
+    """csrc/norm_se3.hip: order M = 2d+1 in {1,3,5,7}; the LDS tile of the
+    gated kernels holds up to NORM_GATED_MAX_C channels."""
+    return M in (1, 3, 5, 7) and not (gated and C > NORM_GATED_MAX_C)
+
+
+RADIAL_TRUNK_DIMS = (1, 2, 3, 5, 9, 17, 21, 25)   # instantiated in csrc/radial.hip
+_KERNEL_DTYPES = (torch.float32, torch.bfloat16)
+
+
+def norm_ok(t, gated: bool, nonlin) -> bool:
+    """nonlin is the kernels' selector ('gelu' | 'identity') or None."""
+    return (nonlin is not None and t.is_cuda and t.dim() >= 2
+            and t.dtype in _KERNEL_DTYPES
+            and norm_shapes_ok(t.shape[-2], t.shape[-1], gated)
+            and not switch_on('SE3_EAGER_NORM') and ext_available())
+
+
+def radial_trunk_ok(in_dim: int, mid_dim: int) -> bool:
+    return mid_dim == 128 and in_dim in RADIAL_TRUNK_DIMS and ext_available()
+
+
+def radial_ok(x, mid_dim: int) -> bool:
+    return (x.is_cuda and not switch_on('SE3_EAGER_RADIAL')
+            and radial_trunk_ok(x.shape[-1], mid_dim))
+
+
+def ubuild_ok(B, C, O, I, F) -> bool:
+    return (B.is_cuda and B.dtype == torch.float32
+            and C % 32 == 0 and O * I * F <= 343
+            and not switch_on('SE3_EAGER_UBUILD') and ext_available())
+
+
+def pairconv_ok(x, mo: int, miF: int, O: int, mid_dim: int) -> bool:
+    """bf16 compute: under autocast, for bf16 features, or SE3_FORCE_FUSED.
+    The one gate that raises when the extension is missing on a GPU."""
+    if not (x.is_cuda
+            and (torch.is_autocast_enabled() or x.dtype == torch.bfloat16
+                 or switch_on('SE3_FORCE_FUSED'))
+            and fused_shapes_ok(mo, miF, O, mid_dim)):
+        return False
+    require_ext()
+    return True
+
+
+def attn_ok(q, J: int, dm: int, rot: int = 0) -> bool:
+    return (q.is_cuda and q.dtype in _KERNEL_DTYPES
+            and attn_shapes_ok(J, dm, rot)
+            and not switch_on('SE3_EAGER_ATTN') and ext_available())
+
+
+def rope_ok(q, j_pre, qpe, kpe, use_null_kv, global_feats) -> bool:
+    """True if the rotary embedding can be folded into the attention kernel
+    (q/k/v rotated in-registers, no rotated copies). The frequency tables
+    must not need grad (rotary_rel_dist with differentiable coors is eager)."""
+    gj = 0
+    if global_feats is not None:   # fiber dict {'0': (b, gj, d, 1)}
+        gj = next(iter(global_feats.values())).shape[1]
+    j_fin = j_pre + (1 if use_null_kv else 0) + gj
+    return (kpe.shape[2] == j_pre
+            and not qpe.requires_grad and not kpe.requires_grad
+            and attn_ok(q, j_fin, q.shape[-2] * q.shape[-1], qpe.shape[-1]))
+
+
+def knn_kernel_ok(coors, n: int, k: int) -> bool:
+    return (coors.is_cuda and coors.dtype == torch.float32 and knn_ok(n, k)
+            and not switch_on('SE3_EAGER_KNN') and ext_available())
+
+
+def sh_basis_ok(r_ij) -> bool:
+    return (r_ij.is_cuda and r_ij.dtype == torch.float32
+            and not switch_on('SE3_EAGER_BASIS') and ext_available())
+
+
+def egnn_ok(nodes, n_htypes: int, max_m: int) -> bool:
+    return (nodes.is_cuda and n_htypes > 0 and max_m <= 7
+            and not switch_on('SE3_EAGER_EGNN') and ext_available())
+
+
+def knn_graph(*args):
+    """csrc/knn.hip: 4 inputs, 4 outputs (idx, dist, rel, m), k, radius, causal."""
+    _load_ext().knn_graph(*args)
 
 
 def _pack_w_fwd(W16, mo, miF):
@@ -127,15 +248,8 @@ def _pack_w_dh(W16, mo, miF):
     return v.permute(0, 2, 5, 6, 1, 3, 7, 4).contiguous()
 
 
-_OPAD = {}
-
-
 def opad(O: int) -> int:
-    """Padded o width OP(O) of the edge-major tensors U (miF, E, OP),
-    G (mo, E, OP) and dU (miF, E, OP): 7, 5 -> 8; 3 -> 4; 1 -> 1. Defined
-    once, in csrc/pairconv_common.h; read from the extension."""
-    if O not in _OPAD:
-        _OPAD[O] = int(_load_ext().pairconv_opad(O))
+    """Padded o width OP(O): 7, 5 -> 8; 3 -> 4; 1 -> 1."""
     return _OPAD[O]
 
 
@@ -167,13 +281,13 @@ class _FusedPairConvOpad(torch.autograd.Function):
         b16 = bias.detach().to(torch.bfloat16).view(mo, miF)
         out = (b16 @ U16.view(miF, E * OP)).view(mo, E, OP)[:, :, :O] \
             .permute(1, 0, 2).contiguous().float()
-        hip_bwd = os.environ.get('SE3_TORCH_BWD') != '1'
+        hip_bwd = not switch_on('SE3_TORCH_BWD')
         # SE3_LOWMEM_PACK=1 trades ~6% step time for memory: save the
         # torch-layout bf16 W (1x) and re-pack in backward, instead of
         # holding both packed fragment layouts (2x) through autograd —
         # frees ~36 GB at the headline 18.2B-param config (enables larger
         # neighbor counts before the activation-memory wall).
-        lowmem = os.environ.get('SE3_LOWMEM_PACK') == '1'
+        lowmem = switch_on('SE3_LOWMEM_PACK')
         if hip_bwd and not lowmem:
             # one-pass pack kernel: W read once, both fragment layouts
             # written; saved for backward so nothing re-packs per step
@@ -210,7 +324,7 @@ class _FusedPairConvOpad(torch.autograd.Function):
         need_H, need_W, need_b, need_u = ctx.needs_input_grad[:4]
 
         ext = _load_ext()
-        if os.environ.get('SE3_TORCH_BWD') != '1':
+        if not switch_on('SE3_TORCH_BWD'):
             dH = dW = db = dU = None
             # one pass: cast, transpose and pad, (mo, E, OP) bf16
             G = torch.empty(mo, E, OP, dtype=torch.bfloat16, device=g.device)
@@ -388,18 +502,18 @@ class _NormSE3GatedFn(torch.autograd.Function):
         return dt, dW, None, None
 
 
-def norm_variants_ok() -> bool:
-    """True when the extension, and with it the identity and gated-scale
-    NormSE3 kernels, is loaded."""
-    return ext_available()
-
-
 def norm_se3(t, scale, eps, nonlin='gelu'):
     return _NormSE3Fn.apply(t, scale, eps, NORM_NONLIN[nonlin])
 
 
 def norm_se3_gated(t, w_gate, eps, nonlin='gelu'):
     return _NormSE3GatedFn.apply(t, w_gate, eps, NORM_NONLIN[nonlin])
+
+
+def _attn_optional(mask_u8, qf, kf, dev):
+    """The kernels take an empty tensor where an optional input is absent."""
+    return [t if t is not None else torch.empty(0, dtype=dtype, device=dev)
+            for t, dtype in ((mask_u8, torch.uint8), (qf, None), (kf, None))]
 
 
 class _AttnFn(torch.autograd.Function):
@@ -416,10 +530,7 @@ class _AttnFn(torch.autograd.Function):
         dev = q.device
         out = torch.empty(R, DM, dtype=torch.float32, device=dev)
         lse = torch.empty(R, dtype=torch.float32, device=dev)
-        m = mask_u8 if mask_u8 is not None else \
-            torch.empty(0, dtype=torch.uint8, device=dev)
-        qf_ = qf if qf is not None else torch.empty(0, device=dev)
-        kf_ = kf if kf is not None else torch.empty(0, device=dev)
+        m, qf_, kf_ = _attn_optional(mask_u8, qf, kf, dev)
         jr = kf.shape[1] if kf is not None else 0
         rot = (qf.shape[-1] if qf is not None
                else (kf.shape[-1] if kf is not None else 0))
@@ -436,10 +547,7 @@ class _AttnFn(torch.autograd.Function):
         n, heads, scale, kv_one, jr, rot = ctx.dims
         R, DM = q.shape
         dev = q.device
-        m = mask_u8 if mask_u8 is not None else \
-            torch.empty(0, dtype=torch.uint8, device=dev)
-        qf_ = qf if qf is not None else torch.empty(0, device=dev)
-        kf_ = kf if kf is not None else torch.empty(0, device=dev)
+        m, qf_, kf_ = _attn_optional(mask_u8, qf, kf, dev)
         dq = torch.empty(R, DM, dtype=torch.float32, device=dev)
         if kv_one:
             # heads share KV rows: the kernel accumulates atomically
@@ -499,11 +607,6 @@ class _UBuildFn(torch.autograd.Function):
             dB = torch.empty(E, O, I, F, dtype=torch.float32, device=B.device)
             ext.ubuild_bwd_db(ctx.saved_tensors[1], dU, dB, O, I, F)
         return dX, dB, None, None, None
-
-
-def ubuild_ok(B, C, O, I, F) -> bool:
-    return (ext_available() and B.dtype == torch.float32
-            and C % 32 == 0 and O * I * F <= 343)
 
 
 def ubuild_opad(x, B, O, I, F):
@@ -585,19 +688,6 @@ def htype_update(ht, idx, w, scale, bias, eps):
     return _HtypeUpdateFn.apply(ht, idx, w, scale, bias, eps)
 
 
-def egnn_kernels_ok(m: int) -> bool:
-    return (ext_available()
-            and m <= 7 and os.environ.get('SE3_EAGER_EGNN') != '1')
-
-
-RADIAL_TRUNK_DIMS = (1, 2, 3, 5, 9, 17, 21, 25)   # instantiated in csrc/radial.hip
-
-
-def radial_trunk_ok(in_dim: int, mid_dim: int) -> bool:
-    return (mid_dim == 128 and in_dim in RADIAL_TRUNK_DIMS
-            and ext_available())
-
-
 class _RadialTrunkFn(torch.autograd.Function):
     """Fused RadialFunc trunk (csrc/radial.hip): Linear(D->128) + LN + GELU
     + Linear(128->128) + LN + GELU in one kernel each way. Mirrors the
@@ -648,3 +738,37 @@ class _RadialTrunkFn(torch.autograd.Function):
 
 def radial_trunk(x, w0, b0, g0, be0, w3, b3, g3, be3, eps=1e-5):
     return _RadialTrunkFn.apply(x, w0, b0, g0, be0, w3, b3, g3, be3, eps)
+
+
+class _ShBasisFn(torch.autograd.Function):
+    """Fused SH + basis kernel with its HIP backward (csrc/sh_basis.hip):
+    rel (E,3) fp32 -> packed basis (E,TOT) fp32, and dK -> d rel. First order
+    only; second-order gradients need the eager path (SE3_EAGER_BASIS=1)."""
+
+    @staticmethod
+    def forward(ctx, rel, qcat, normtab, meta, TOT, L):
+        out = torch.empty(rel.shape[0], TOT, dtype=torch.float32, device=rel.device)
+        _load_ext().sh_basis_fwd(rel, qcat, normtab, meta, out, L)
+        ctx.save_for_backward(rel, qcat, normtab, meta)
+        ctx.L = L
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dK):
+        rel, qcat, normtab, meta = ctx.saved_tensors
+        drel = torch.empty_like(rel)
+        _load_ext().sh_basis_bwd(rel, qcat, normtab, meta,
+                                 dK.contiguous().float(), drel, ctx.L)
+        return drel, None, None, None, None, None
+
+
+def sh_basis(rel, qcat, normtab, meta, TOT, L, differentiable):
+    """Packed basis (E, TOT) fp32 of rel (E, 3) fp32. With differentiable
+    set, and rel requiring grad, the result carries a first-order autograd
+    edge to rel; otherwise it is detached."""
+    if differentiable and rel.requires_grad and torch.is_grad_enabled():
+        return _ShBasisFn.apply(rel, qcat, normtab, meta, TOT, L)
+    out = torch.empty(rel.shape[0], TOT, dtype=torch.float32, device=rel.device)
+    _load_ext().sh_basis_fwd(rel.detach(), qcat, normtab, meta, out, L)
+    return out

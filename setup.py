@@ -23,7 +23,8 @@ setup(
     ext_modules=[
         CUDAExtension(
             name='se3_transformer_amd._C',
-            sources=['se3_transformer_amd/csrc/pairconv.hip',
+            sources=['se3_transformer_amd/csrc/bindings.cpp',
+                     'se3_transformer_amd/csrc/pairconv.hip',
                      'se3_transformer_amd/csrc/pairconv_bwd.hip',
                      'se3_transformer_amd/csrc/pack_w.hip',
                      'se3_transformer_amd/csrc/radial.hip',

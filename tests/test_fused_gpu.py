@@ -3,10 +3,10 @@
 The kernel computes in bf16 with fp32 accumulation; parity is checked
 against an fp32 eager reference with bf16-grade tolerance bands.
 """
-import os
-
 import pytest
 import torch
+
+from fused_helpers import switches
 
 pytestmark = pytest.mark.gpu
 
@@ -44,11 +44,8 @@ def test_pairconv_kernel_vs_eager(di, do):
 
     ref = pc.apply_fused(ef, {(di, do): b}, xg).float()
 
-    os.environ['SE3_FORCE_FUSED'] = '1'
-    try:
+    with switches(SE3_FORCE_FUSED='1'):
         out = pc.apply_fused(ef, {(di, do): b}, xg.clone()).float()
-    finally:
-        del os.environ['SE3_FORCE_FUSED']
     err = _rel_err(out, ref)
     assert err < 5e-2, f'forward parity {err}'
 
@@ -77,12 +74,9 @@ def test_pairconv_kernel_backward_parity():
     gx_ref = xg0.grad.clone()
     pc.zero_grad()
 
-    os.environ['SE3_FORCE_FUSED'] = '1'
-    try:
+    with switches(SE3_FORCE_FUSED='1'):
         out = pc.apply_fused(ef, {(di, do): b}, xg1).float()
         out.pow(2).mean().backward()
-    finally:
-        del os.environ['SE3_FORCE_FUSED']
     gw = pc.rp.net[6].weight.grad.clone()
     gb = pc.rp.net[6].bias.grad.clone()
     g0 = pc.rp.net[0].weight.grad.clone()
@@ -116,15 +110,10 @@ def test_hip_bwd_vs_torch_bwd(di, do):
                          generator=torch.Generator(device).manual_seed(7),
                          requires_grad=True)
         pc.zero_grad()
-        os.environ['SE3_FORCE_FUSED'] = '1'
-        if mode == 'torch':
-            os.environ['SE3_TORCH_BWD'] = '1'
-        try:
+        with switches(SE3_FORCE_FUSED='1',
+                      SE3_TORCH_BWD='1' if mode == 'torch' else None):
             out = pc.apply_fused(ef, {(di, do): b}, xg).float()
             out.pow(2).mean().backward()
-        finally:
-            del os.environ['SE3_FORCE_FUSED']
-            os.environ.pop('SE3_TORCH_BWD', None)
         grads[mode] = {
             'x': xg.grad.clone(),
             'w6': pc.rp.net[6].weight.grad.clone(),
@@ -157,15 +146,11 @@ def test_model_fused_bf16_close_to_eager_fp32():
 @needs_gpu
 @pytest.mark.parametrize('max_degree', [1, 2, 3])
 def test_sh_basis_kernel_vs_eager(max_degree):
-    import os as _os
     from se3_transformer_amd.ops.basis import get_basis_packed
     torch.manual_seed(3)
     rel = torch.randn(2, 100, 8, 3, device='cuda')
-    _os.environ['SE3_EAGER_BASIS'] = '1'
-    try:
+    with switches(SE3_EAGER_BASIS='1'):
         ref = get_basis_packed(rel, max_degree)
-    finally:
-        del _os.environ['SE3_EAGER_BASIS']
     fast = get_basis_packed(rel, max_degree)
     assert set(ref) == set(fast)
     for k in ref:
@@ -176,7 +161,6 @@ def test_sh_basis_kernel_vs_eager(max_degree):
 @needs_gpu
 @pytest.mark.parametrize('m', [1, 3, 7])
 def test_norm_se3_kernel_vs_eager(m):
-    import os as _os
     from se3_transformer_amd.models.core import NormSE3
     from se3_transformer_amd.models.fiber import Fiber
     torch.manual_seed(4)
@@ -185,11 +169,8 @@ def test_norm_se3_kernel_vs_eager(m):
     t0 = torch.randn(3, 50, 24, m, device='cuda', requires_grad=True)
     t1 = t0.detach().clone().requires_grad_(True)
 
-    _os.environ['SE3_EAGER_NORM'] = '1'
-    try:
+    with switches(SE3_EAGER_NORM='1'):
         ref = norm({str(degree): t0})[str(degree)]
-    finally:
-        del _os.environ['SE3_EAGER_NORM']
     ref.pow(2).mean().backward()
     out = norm({str(degree): t1})[str(degree)]
     assert _rel_err(out, ref) < 1e-5
@@ -203,7 +184,6 @@ def test_norm_se3_kernel_vs_eager(m):
 
 @needs_gpu
 def test_fused_attention_vs_eager():
-    import os as _os
     from se3_transformer_amd.models.attention import AttentionSE3
     from se3_transformer_amd.models.fiber import Fiber
     torch.manual_seed(5)
@@ -222,11 +202,8 @@ def test_fused_attention_vs_eager():
     basis = get_basis_packed(rel_pos, 1)
     edge_info = (nbr_idx, nbr_mask, None)
 
-    _os.environ['SE3_EAGER_ATTN'] = '1'
-    try:
+    with switches(SE3_EAGER_ATTN='1'):
         ref = attn(feats, edge_info, rel_dist, basis)
-    finally:
-        del _os.environ['SE3_EAGER_ATTN']
     (ref['0'].pow(2).mean() + ref['1'].pow(2).mean()).backward()
     gref = {k: v.grad.clone() for k, v in feats.items()}
 
@@ -240,7 +217,6 @@ def test_fused_attention_vs_eager():
 
 @needs_gpu
 def test_knn_kernel_vs_eager():
-    import os as _os
     from se3_transformer_amd import SE3Transformer
     torch.manual_seed(6)
     model = SE3Transformer(dim=32, heads=2, dim_head=16, depth=1,
@@ -249,11 +225,8 @@ def test_knn_kernel_vs_eager():
     feats = torch.randn(2, 50, 32, device='cuda')
     coors = torch.randn(2, 50, 3, device='cuda') * 1.3
     mask = torch.rand(2, 50, device='cuda') > 0.1
-    _os.environ['SE3_EAGER_KNN'] = '1'
-    try:
+    with switches(SE3_EAGER_KNN='1'):
         ref = model(feats, coors, mask, return_type=0)
-    finally:
-        del _os.environ['SE3_EAGER_KNN']
     out = model(feats, coors, mask, return_type=0)
     err = (out - ref).abs().max().item()
     assert err < 1e-4, f'knn path mismatch: {err}'
@@ -261,7 +234,6 @@ def test_knn_kernel_vs_eager():
 
 @needs_gpu
 def test_fused_attention_one_headed_vs_eager():
-    import os as _os
     from se3_transformer_amd.models.attention import OneHeadedKVAttentionSE3
     from se3_transformer_amd.models.fiber import Fiber
     from se3_transformer_amd.ops.basis import get_basis_packed
@@ -278,11 +250,8 @@ def test_fused_attention_one_headed_vs_eager():
     rel_dist = torch.rand(b, n, kn, device='cuda')
     basis = get_basis_packed(torch.randn(b, n, kn, 3, device='cuda'), 1)
 
-    _os.environ['SE3_EAGER_ATTN'] = '1'
-    try:
+    with switches(SE3_EAGER_ATTN='1'):
         ref = attn(feats, edge_info, rel_dist, basis)
-    finally:
-        del _os.environ['SE3_EAGER_ATTN']
     (ref['0'].pow(2).mean() + ref['1'].pow(2).mean()).backward()
     gref = {k: v.grad.clone() for k, v in feats.items()}
 
@@ -296,7 +265,6 @@ def test_fused_attention_one_headed_vs_eager():
 
 @needs_gpu
 def test_knn_kernel_causal_vs_eager():
-    import os as _os
     from se3_transformer_amd import SE3Transformer
     torch.manual_seed(8)
     model = SE3Transformer(dim=32, heads=2, dim_head=16, depth=1,
@@ -305,11 +273,8 @@ def test_knn_kernel_causal_vs_eager():
     feats = torch.randn(1, 40, 32, device='cuda')
     coors = torch.randn(1, 40, 3, device='cuda')
     mask = torch.ones(1, 40, dtype=torch.bool, device='cuda')
-    _os.environ['SE3_EAGER_KNN'] = '1'
-    try:
+    with switches(SE3_EAGER_KNN='1'):
         ref = model(feats, coors, mask, return_type=0)
-    finally:
-        del _os.environ['SE3_EAGER_KNN']
     out = model(feats, coors, mask, return_type=0)
     err = (out - ref).abs().max().item()
     assert err < 1e-4, f'causal knn mismatch: {err}'
@@ -338,13 +303,13 @@ def test_pack_w_both_matches_python_permutes():
 
 
 def _fwd_mo16(O, mb2):
-    """pairconv_fwd at mo=16, miF=160, E=500 on fixed inputs: mb2=2 is one
+    """pairconv_fwd_opad at mo=16, miF=160, E=500 on fixed inputs: mb2=2 is one
     launch (two mo-blocks per workgroup, picked when mo % 16 == 0); mb2=1
     is two mo=8 launches (the one-block kernel) over the contiguous halves
     of the packed W, whose leading index is the mo-block, written into the
     matching halves of the output."""
     from se3_transformer_amd import _C
-    from se3_transformer_amd.ops.fused import _pack_w_fwd
+    from se3_transformer_amd.ops.fused import _pack_w_fwd, _to_opad
 
     device = torch.device('cuda')
     g = torch.Generator(device).manual_seed(4)
@@ -353,14 +318,15 @@ def _fwd_mo16(O, mb2):
     W = torch.randn(mo * miF, 128, generator=g, device=device).to(torch.bfloat16)
     Ut = torch.randn(miF, O, E, generator=g, device=device).to(torch.bfloat16)
     P = _pack_w_fwd(W, mo, miF).reshape(2, -1)
+    U = _to_opad(Ut, O)
 
     out = torch.zeros(E, mo, O, device=device)
     if mb2 == 2:
-        _C.pairconv_fwd(H, P, Ut, out, mo)
+        _C.pairconv_fwd_opad(H, P, U, out, mo)
         return out
     for half in range(2):
         out_h = torch.zeros(E, mo // 2, O, device=device)
-        _C.pairconv_fwd(H, P[half], Ut, out_h, mo // 2)
+        _C.pairconv_fwd_opad(H, P[half], U, out_h, mo // 2)
         out[:, half * 8:(half + 1) * 8] = out_h
     return out
 
@@ -465,11 +431,8 @@ def test_radial_trunk_kernel_vs_eager(edge_in):
     x0 = torch.randn(E, edge_in, device=device, requires_grad=True)
     x1 = x0.detach().clone().requires_grad_(True)
 
-    os.environ['SE3_EAGER_RADIAL'] = '1'
-    try:
+    with switches(SE3_EAGER_RADIAL='1'):
         ref = rp.hidden(x0)
-    finally:
-        del os.environ['SE3_EAGER_RADIAL']
     ref.pow(2).mean().backward()
     ref_grads = {n: p.grad.clone() for n, p in rp.named_parameters()
                  if p.grad is not None}
@@ -519,14 +482,10 @@ def test_attn2_module_vs_eager_with_backward(kn):
                                   requires_grad=True),
                  '1': torch.randn(b, n, 16, 3, device='cuda',
                                   requires_grad=True)}
-        if mode == 'eager':
-            os.environ['SE3_EAGER_ATTN'] = '1'
-        try:
+        with switches(SE3_EAGER_ATTN='1' if mode == 'eager' else None):
             out = attn(feats, (nbr_idx, nbr_mask, None), rel_dist, basis)
             loss = sum(t.pow(2).mean() for t in out.values())
             loss.backward()
-        finally:
-            os.environ.pop('SE3_EAGER_ATTN', None)
         results[mode] = {'out0': out['0'].detach().clone(),
                          'out1': out['1'].detach().clone(),
                          'g0': feats['0'].grad.clone(),
@@ -550,12 +509,9 @@ def test_attn2_rotary_in_kernel_vs_eager():
     feats = torch.randn(2, 48, 32, device='cuda')
     coors = torch.randn(2, 48, 3, device='cuda')
     mask = torch.ones(2, 48, dtype=torch.bool, device='cuda')
-    os.environ['SE3_EAGER_ATTN'] = '1'
-    try:
+    with switches(SE3_EAGER_ATTN='1'):
         ref = model(feats, coors, mask, return_type=0)
         ref.pow(2).mean().backward()
-    finally:
-        del os.environ['SE3_EAGER_ATTN']
     gref = {n: p.grad.clone() for n, p in model.named_parameters()
             if p.grad is not None}
     model.zero_grad()
@@ -574,7 +530,6 @@ def test_attn2_rotary_in_kernel_vs_eager():
 def test_knn_kernel_large_k_and_neighbor_mask():
     """kNN kernel with k > 16 and a user neighbor_mask restricting
     candidate selection (both round-2 extensions), vs the eager build."""
-    import os as _os
     from se3_transformer_amd import SE3Transformer
     torch.manual_seed(11)
     model = SE3Transformer(dim=32, heads=2, dim_head=16, depth=1,
@@ -585,11 +540,8 @@ def test_knn_kernel_large_k_and_neighbor_mask():
     coors = torch.randn(b, n, 3, device='cuda') * 1.5
     mask = torch.ones(b, n, dtype=torch.bool, device='cuda')
     nbr_allow = torch.rand(b, n, n, device='cuda') > 0.3
-    _os.environ['SE3_EAGER_KNN'] = '1'
-    try:
+    with switches(SE3_EAGER_KNN='1'):
         ref = model(feats, coors, mask, neighbor_mask=nbr_allow, return_type=0)
-    finally:
-        del _os.environ['SE3_EAGER_KNN']
     out = model(feats, coors, mask, neighbor_mask=nbr_allow, return_type=0)
     err = (out - ref).abs().max().item()
     assert err < 1e-4, f'large-k/neighbor_mask knn mismatch: {err}'
@@ -599,7 +551,6 @@ def test_knn_kernel_large_k_and_neighbor_mask():
 def test_knn_kernel_sparse_adjacency():
     """kNN kernel with attend_sparse_neighbors + adjacency embeddings
     (qm9-style config) vs the eager build."""
-    import os as _os
     from se3_transformer_amd import SE3Transformer
     torch.manual_seed(12)
     model = SE3Transformer(dim=32, heads=2, dim_head=16, depth=1,
@@ -612,11 +563,8 @@ def test_knn_kernel_sparse_adjacency():
     feats = torch.randn(b, n, 32, device='cuda')
     coors = torch.randn(b, n, 3, device='cuda')
     mask = torch.ones(b, n, dtype=torch.bool, device='cuda')
-    _os.environ['SE3_EAGER_KNN'] = '1'
-    try:
+    with switches(SE3_EAGER_KNN='1'):
         ref = model(feats, coors, mask, adj_mat=adj_mat, return_type=0)
-    finally:
-        del _os.environ['SE3_EAGER_KNN']
     out = model(feats, coors, mask, adj_mat=adj_mat, return_type=0)
     err = (out - ref).abs().max().item()
     assert err < 1e-4, f'sparse-adjacency knn mismatch: {err}'
@@ -660,12 +608,9 @@ def test_egnn_kernels_vs_eager():
     coors = torch.randn(2, 32, 3, device='cuda')
     mask = torch.ones(2, 32, dtype=torch.bool, device='cuda')
 
-    os.environ['SE3_EAGER_EGNN'] = '1'
-    try:
+    with switches(SE3_EAGER_EGNN='1'):
         ref = model(feats, coors, mask, return_type=1)
         ref.pow(2).mean().backward()
-    finally:
-        del os.environ['SE3_EAGER_EGNN']
     gref = {n: p.grad.clone() for n, p in model.named_parameters()
             if p.grad is not None}
     model.zero_grad()
@@ -719,11 +664,8 @@ def test_lowmem_pack_mode_matches_default():
         return out.detach(), H.grad, W.grad, bias.grad, Ut.grad
 
     ref = run()
-    os.environ['SE3_LOWMEM_PACK'] = '1'
-    try:
+    with switches(SE3_LOWMEM_PACK='1'):
         low = run()
-    finally:
-        del os.environ['SE3_LOWMEM_PACK']
     names = ('out', 'dH', 'dW', 'db', 'dUt')
     for name, a, b in zip(names, low, ref):
         if name == 'dH':   # split-K atomics: order noise only

@@ -4,6 +4,7 @@ any 1 <= k <= n-1 whose LDS footprint, min(k, ceil(n/64)) * 512 + 4k bytes
 KNN_MAX_LDS."""
 import pytest
 
+from fused_helpers import install_ext, stub_ext
 from se3_transformer_amd.ops import fused
 
 
@@ -32,20 +33,18 @@ def test_knn_ok_matches_lds_formula():
 
 def test_stale_budget_is_an_error_on_first_use(monkeypatch):
     """KNN_MAX_LDS must be the budget the built kernel enforces: a module
-    that reports another one is refused before its kernel is called."""
-    import types
+    that reports another one is refused at load, before its kernel is
+    called."""
     called = []
-    mod = types.SimpleNamespace(knn_max_lds_bytes=lambda: 32768,
-                                knn_graph=lambda *a: called.append(a))
-    monkeypatch.setattr(fused, '_EXT', mod)
-    monkeypatch.setattr(fused, '_EXT_ERR', None)
-    monkeypatch.setattr(fused, '_KNN_BUDGET_CHECKED', False)
+    mod = stub_ext(knn_lds=32768)
+    mod.knn_graph = lambda *a: called.append(a)
+    install_ext(monkeypatch, mod)
     with pytest.raises(RuntimeError, match='knn_max_lds_bytes'):
         fused.knn_graph(*[None] * 11)
     assert not called
     mod.knn_max_lds_bytes = lambda: fused.KNN_MAX_LDS
     fused.knn_graph(*[None] * 11)
-    assert len(called) == 1 and fused._KNN_BUDGET_CHECKED
+    assert len(called) == 1 and fused._load_ext() is mod
 
 
 def test_budget_boundary():

@@ -6,12 +6,12 @@ w_gate is set to randn(C, C)/sqrt(C): the default +-1e-3 init leaves
 gate ~ 0, which tests nothing.
 """
 import math
-import os
-from contextlib import contextmanager
 
 import pytest
 import torch
 from torch import nn
+
+from fused_helpers import switches
 
 pytestmark = pytest.mark.gpu
 
@@ -23,15 +23,6 @@ NONLINS = {'gelu': nn.GELU, 'identity': nn.Identity}
 def _rel_err(a, b):
     denom = b.abs().max().clamp(min=1e-6)
     return ((a - b).abs().max() / denom).item()
-
-
-@contextmanager
-def _eager_norm():
-    os.environ['SE3_EAGER_NORM'] = '1'
-    try:
-        yield
-    finally:
-        del os.environ['SE3_EAGER_NORM']
 
 
 def _make(C, m, nonlin, gated, eps=1e-12, seed=0, device='cuda'):
@@ -77,7 +68,7 @@ def _run(mod, key, t, dout=None, eager=False):
     t = t.detach().clone().requires_grad_(True)
     mod.zero_grad()
     if eager:
-        with _eager_norm():
+        with switches(SE3_EAGER_NORM='1'):
             out = mod({key: t})[key]
     else:
         out = mod({key: t})[key]
@@ -118,7 +109,7 @@ def test_variants_reach_the_fused_path(monkeypatch):
     for name in ('norm_se3_nl_fwd', 'norm_se3_nl_bwd',
                  'norm_se3_gated_fwd', 'norm_se3_gated_bwd'):
         assert hasattr(ext, name), f'extension lacks {name}'
-    assert fused.norm_variants_ok()
+    assert fused.ext_available()
 
     cnt = _Counter(monkeypatch)
     t = torch.randn(2, 5, 24, 3, device='cuda')
@@ -133,7 +124,7 @@ def test_variants_reach_the_fused_path(monkeypatch):
     assert cnt.n['norm_se3'] == before + 1
 
     total = cnt.total
-    with _eager_norm():
+    with switches(SE3_EAGER_NORM='1'):
         for nonlin in ('gelu', 'identity'):
             for gated in (True, False):
                 mod, key = _make(24, 3, nonlin, gated=gated)
@@ -254,7 +245,7 @@ def test_fallbacks_stay_eager(monkeypatch):
 
     def same_as_oracle(mod, key, t):
         out = mod({key: t})[key]
-        with _eager_norm():
+        with switches(SE3_EAGER_NORM='1'):
             ref = mod({key: t})[key]
         assert torch.equal(out, ref)
 
@@ -323,7 +314,7 @@ def test_model_gated_norm_vs_eager(reversible, monkeypatch):
                               for n, p in model.named_parameters()
                               if p.grad is not None}
 
-    with _eager_norm():
+    with switches(SE3_EAGER_NORM='1'):
         ref, gref = run()
     assert cnt.total == 0
     out, grads = run()
