@@ -27,6 +27,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     OP(ubuild_fwd, "basis x features precontraction, out (C*F, E, OP)");
     OP(ubuild_bwd_dx, "ubuild dX backward");
     OP(ubuild_bwd_db, "ubuild dB backward (differentiable coordinates)");
+    OP(ubuild_gather_fwd, "ubuild_fwd on node features: X[e] = Xn[rows[e]]");
+    OP(ubuild_gather_bwd_dx, "its dXn backward: fp32 atomic adds into (N, C, I)");
+    OP(ubuild_gather_bwd_db, "ubuild_bwd_db on node features");
     OP(egnn_rel_dist_fwd, "EGNN neighbor rel-htype distances (no n^2 intermediate)");
     OP(egnn_rel_dist_bwd, "its backward");
     OP(egnn_htype_update_fwd, "EGNN htype norm+weighted neighbor sum (no n^2 intermediate)");

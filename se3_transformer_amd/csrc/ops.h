@@ -25,6 +25,12 @@ void radial_trunk_bwd(Tensor dH, Tensor X, Tensor W0, Tensor p0, Tensor W3, Tens
 void ubuild_fwd(Tensor B, Tensor X, Tensor U, int64_t O, int64_t I, int64_t F);
 void ubuild_bwd_dx(Tensor B, Tensor dU, Tensor dX, int64_t O, int64_t I, int64_t F);
 void ubuild_bwd_db(Tensor X, Tensor dU, Tensor dB, int64_t O, int64_t I, int64_t F);
+void ubuild_gather_fwd(Tensor B, Tensor Xn, Tensor rows, Tensor U, int64_t O, int64_t I,
+                       int64_t F);
+void ubuild_gather_bwd_dx(Tensor B, Tensor dU, Tensor rows, Tensor dXn, int64_t O,
+                          int64_t I, int64_t F);
+void ubuild_gather_bwd_db(Tensor Xn, Tensor rows, Tensor dU, Tensor dB, int64_t O,
+                          int64_t I, int64_t F);
 // sh_basis.hip
 void sh_basis_fwd(Tensor rel, Tensor qcat, Tensor normtab, Tensor meta, Tensor out,
                   int64_t L);

@@ -22,6 +22,14 @@
 // rather than a second output of the dX kernel: the dX kernel's LDS already
 // holds B and a dU tile, and adding the fp32 dB tile would pass 64 KiB for
 // the (7,7,7) pair. The price is one extra read of dU on that path only.
+//
+// The ubuild_gather_* entry points take x per NODE, Xn (N, C, I), and the
+// row of every edge, rows (E,) int32: X[e] = Xn[rows[e]] without the gathered
+// (E, C, I) tensor. Forward and dB are the kernels above with an indexed
+// staging load (same bits). dXn (N, C, I) fp32 is summed over the edges of a
+// row with atomicAdd: the backward of the gather, and the sum over the pairs
+// that share a d_in when they accumulate into one buffer. An edge whose row
+// is outside [0, N) reads x as zero and adds nothing.
 
 #include <hip/hip_runtime.h>
 #include "host_common.h"
@@ -36,12 +44,26 @@
 
 typedef __attribute__((ext_vector_type(2))) __bf16 ub_bf16x2;
 
-template <typename TX, int OP>
-__global__ void __launch_bounds__(UB_NT)
-ubuild_fwd_kernel(const float* __restrict__ B,   // (E, O, I, F)
-                  const TX* __restrict__ X,      // (E, C, I)
-                  __bf16* __restrict__ Ut,       // (C*F, E, OP)
-                  int E, int C, int O, int I, int F) {
+// Row of X that holds edge e's features: e itself, or rows[e] of the
+// N-row node tensor. -1 past the last edge (and for a row outside [0, N)).
+template <bool GATHER>
+__device__ __forceinline__ long ub_x_row(const int* __restrict__ rows, int e,
+                                         int E, int N) {
+    if (e >= E) return -1;
+    if constexpr (!GATHER) return e;
+    else {
+        int r = rows[e];
+        return ((unsigned)r < (unsigned)N) ? r : -1;
+    }
+}
+
+template <typename TX, int OP, bool GATHER>
+__device__ __forceinline__ void
+ubuild_fwd_body(const float* __restrict__ B,   // (E, O, I, F)
+                const TX* __restrict__ X,      // (E, C, I) | (N, C, I)
+                const int* __restrict__ rows,  // (E,) when GATHER
+                __bf16* __restrict__ Ut,       // (C*F, E, OP)
+                int E, int N, int C, int O, int I, int F) {
     // b and x tiles are stored [.., i PADDED to 8] bf16 so each output
     // element is two 16B LDS reads + 4 v_dot2_f32_bf16 over i
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -65,14 +87,19 @@ ubuild_fwd_kernel(const float* __restrict__ B,   // (E, O, I, F)
             (__bf16)((e0 + e < E) ? B[(size_t)(e0 + e) * oif + r] : 0.f);
     }
 
+    // the staging loop below strides by UB_NT = UB_E * 8: a thread stages
+    // the same (e, i) of every channel, so its x row is fixed
+    static_assert(UB_NT == UB_E * 8, "x staging: one (e, i) per thread");
+    const long xr = ub_x_row<GATHER>(rows, e0 + tid / 8, E, N);
+
     for (int c0 = 0; c0 < C; c0 += UB_C) {
         __syncthreads();   // previous chunk's compute done with x_lds
         for (int t = tid; t < UB_C * UB_E * 8; t += UB_NT) {
             int c = t / (UB_E * 8), rem = t % (UB_E * 8);
             int e = rem / 8, i = rem % 8;
             x_lds[((size_t)c * UB_E + e) * 8 + i] = (__bf16)(
-                (i < I && e0 + e < E)
-                    ? (float)X[((size_t)(e0 + e) * C + c0 + c) * I + i] : 0.f);
+                (i < I && xr >= 0)
+                    ? (float)X[((size_t)xr * C + c0 + c) * I + i] : 0.f);
         }
         __syncthreads();
         // out vectors of this chunk: (c 32) x (f F) x (e 32), e minor; the
@@ -108,6 +135,21 @@ ubuild_fwd_kernel(const float* __restrict__ B,   // (E, O, I, F)
             }
         }
     }
+}
+
+template <typename TX, int OP>
+__global__ void __launch_bounds__(UB_NT)
+ubuild_fwd_kernel(const float* __restrict__ B, const TX* __restrict__ X,
+                  __bf16* __restrict__ Ut, int E, int C, int O, int I, int F) {
+    ubuild_fwd_body<TX, OP, false>(B, X, nullptr, Ut, E, E, C, O, I, F);
+}
+
+template <typename TX, int OP>
+__global__ void __launch_bounds__(UB_NT)
+ubuild_gather_fwd_kernel(const float* __restrict__ B, const TX* __restrict__ Xn,
+                         const int* __restrict__ rows, __bf16* __restrict__ Ut,
+                         int E, int N, int C, int O, int I, int F) {
+    ubuild_fwd_body<TX, OP, true>(B, Xn, rows, Ut, E, N, C, O, I, F);
 }
 
 template <typename TX>
@@ -170,12 +212,13 @@ ubuild_bwd_dx_kernel(const float* __restrict__ B,   // (E, O, I, F)
 // rounding of B and X.
 #define UB_DBK 22        // ceil(16 * 343 / 256)
 
-template <typename TX>
-__global__ void __launch_bounds__(UB_NT)
-ubuild_bwd_db_kernel(const TX* __restrict__ X,      // (E, C, I)
-                     const float* __restrict__ dU,  // (C*F, E, OP) f32
-                     float* __restrict__ dB,        // (E, O, I, F)
-                     int E, int C, int O, int I, int F) {
+template <typename TX, bool GATHER>
+__device__ __forceinline__ void
+ubuild_bwd_db_body(const TX* __restrict__ X,      // (E, C, I) | (N, C, I)
+                   const int* __restrict__ rows,  // (E,) when GATHER
+                   const float* __restrict__ dU,  // (C*F, E, OP) f32
+                   float* __restrict__ dB,        // (E, O, I, F)
+                   int E, int N, int C, int O, int I, int F) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* g_lds = reinterpret_cast<float*>(smem);            // [8c][F*O][16e]
     float* x_lds = g_lds + UB_CB * F * O * UB_EB;             // [8c][I][16e]
@@ -200,6 +243,9 @@ ubuild_bwd_db_kernel(const TX* __restrict__ X,      // (E, C, I)
         offs[k] = (i * UB_EB + e) | (((f * O + o) * UB_EB + e) << 10);
         acc[k] = 0.f;
     }
+    // x staging strides by UB_NT, a multiple of UB_EB: one e per thread
+    static_assert(UB_NT % UB_EB == 0, "x staging: one e per thread");
+    const long xr = ub_x_row<GATHER>(rows, e0 + tid % UB_EB, E, N);
 
     for (int c0 = 0; c0 < C; c0 += UB_CB) {
         __syncthreads();
@@ -214,11 +260,10 @@ ubuild_bwd_db_kernel(const TX* __restrict__ X,      // (E, C, I)
                     ? dU[(((size_t)(c0 + c) * F + f) * E + e0 + e) * OP + o] : 0.f;
         }
         for (int t = tid; t < UB_CB * I * UB_EB; t += UB_NT) {
-            int e = t % UB_EB;
             int r = t / UB_EB;         // c*I + i
             int c = r / I, i = r % I;
-            x_lds[t] = (e0 + e < E)
-                ? (float)X[((size_t)(e0 + e) * C + c0 + c) * I + i] : 0.f;
+            x_lds[t] = (xr >= 0)
+                ? (float)X[((size_t)xr * C + c0 + c) * I + i] : 0.f;
         }
         __syncthreads();
 #pragma unroll
@@ -241,6 +286,87 @@ ubuild_bwd_db_kernel(const TX* __restrict__ X,      // (E, C, I)
         int e = t % UB_EB, r = t / UB_EB;
         if (t < nout && e0 + e < E)
             dB[(size_t)(e0 + e) * oif + r] = acc[k];
+    }
+}
+
+template <typename TX>
+__global__ void __launch_bounds__(UB_NT)
+ubuild_bwd_db_kernel(const TX* __restrict__ X, const float* __restrict__ dU,
+                     float* __restrict__ dB, int E, int C, int O, int I, int F) {
+    ubuild_bwd_db_body<TX, false>(X, nullptr, dU, dB, E, E, C, O, I, F);
+}
+
+template <typename TX>
+__global__ void __launch_bounds__(UB_NT)
+ubuild_gather_bwd_db_kernel(const TX* __restrict__ Xn,
+                            const int* __restrict__ rows,
+                            const float* __restrict__ dU,
+                            float* __restrict__ dB,
+                            int E, int N, int C, int O, int I, int F) {
+    ubuild_bwd_db_body<TX, true>(Xn, rows, dU, dB, E, N, C, O, I, F);
+}
+
+// dXn[rows[e], c, i] += sum_{f,o} B[e,o,i,f] * dU[(c*F+f), e, o]
+//
+// The arithmetic of ubuild_bwd_dx_kernel, mapped for the atomics: a
+// destination row is contiguous over (c, i), so the threads of a chunk run
+// (c, i) minor, e major, and a wave's 64 adds are contiguous runs of CB*I
+// floats (CB is chosen by the host so a run is at least 128 B): two rows
+// per instruction, three where a 40- or 48-float run straddles, not 16. The dU tile sits [e][c][f*O+o]: lanes differ in c, F*O is odd, so
+// the compute reads are conflict-free.
+template <int CB>
+__global__ void __launch_bounds__(UB_NT)
+ubuild_gather_bwd_dx_kernel(const float* __restrict__ B,   // (E, O, I, F)
+                            const float* __restrict__ dU,  // (C*F, E, OP) f32
+                            const int* __restrict__ rows,  // (E,)
+                            float* __restrict__ dXn,       // (N, C, I) f32
+                            int E, int N, int C, int O, int I, int F) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ int r_lds[UB_EB];
+    float* b_lds = reinterpret_cast<float*>(smem);            // [16e][O*I*F]
+    float* g_lds = b_lds + UB_EB * O * I * F;                 // [16e][CB c][F*O]
+
+    const int tid = threadIdx.x;
+    const int e0 = blockIdx.x * UB_EB;
+    const int oif = O * I * F;
+    const int fo = F * O;
+    const int OP = opad_of(O);
+
+    if (tid < UB_EB) r_lds[tid] = (int)ub_x_row<true>(rows, e0 + tid, E, N);
+    for (int t = tid; t < UB_EB * oif; t += UB_NT) {
+        int e = t / oif, r = t % oif;
+        b_lds[e * oif + r] = (e0 + e < E) ? B[(size_t)(e0 + e) * oif + r] : 0.f;
+    }
+
+    for (int c0 = 0; c0 < C; c0 += CB) {
+        __syncthreads();
+        // dU tile, read in memory order (o minor, pads skipped)
+        for (int t = tid; t < CB * F * UB_EB * OP; t += UB_NT) {
+            int o = t % OP;
+            int r = t / OP;
+            int e = r % UB_EB;
+            int cf = r / UB_EB;        // c*F + f
+            int c = cf / F, f = cf % F;
+            if (o < O)
+                g_lds[(e * CB + c) * fo + f * O + o] = (e0 + e < E)
+                    ? dU[(((size_t)(c0 + c) * F + f) * E + e0 + e) * OP + o] : 0.f;
+        }
+        __syncthreads();
+        // dXn elements: (e 16) x (c CB) x (i I), (c, i) minor as in memory
+        const int run = CB * I;
+        for (int t = tid; t < UB_EB * run; t += UB_NT) {
+            int e = t / run, ci = t % run;
+            int c = ci / I, i = ci % I;
+            float acc = 0.f;
+            const float* g = g_lds + (e * CB + c) * fo;
+            const float* b = b_lds + e * oif + i * F;
+            for (int f = 0; f < F; ++f)
+                for (int o = 0; o < O; ++o)
+                    acc = fmaf(b[(size_t)o * I * F + f], g[f * O + o], acc);
+            int row = r_lds[e];
+            if (row >= 0)
+                atomicAdd(&dXn[((size_t)row * C + c0) * I + ci], acc);
+        }
     }
 }
 
@@ -327,4 +453,120 @@ void ubuild_bwd_db(torch::Tensor X, torch::Tensor dU, torch::Tensor dB,
                            E, C, (int)O, (int)I, (int)F);
     });
     check_launch("ubuild_bwd_db: ");
+}
+
+// The checks the three gather entry points share; returns N.
+static int check_gather(const torch::Tensor& Xn, const torch::Tensor& rows,
+                        int64_t E, int64_t I) {
+    TORCH_CHECK(Xn.is_cuda() && Xn.is_contiguous() && Xn.dim() == 3 &&
+                Xn.size(2) == I, "expect Xn as (N, C, I), contiguous");
+    TORCH_CHECK(rows.is_cuda() && rows.is_contiguous() &&
+                rows.dtype() == torch::kInt32 && rows.numel() == E,
+                "expect rows as (E,) int32, contiguous");
+    TORCH_CHECK(Xn.size(0) < (1LL << 31));
+    return (int)Xn.size(0);
+}
+
+void ubuild_gather_fwd(torch::Tensor B, torch::Tensor Xn, torch::Tensor rows,
+                       torch::Tensor Ut, int64_t O, int64_t I, int64_t F) {
+    TORCH_CHECK(B.is_cuda() && B.is_contiguous() && B.dtype() == torch::kFloat32);
+    TORCH_CHECK(Ut.is_cuda() && Ut.is_contiguous() &&
+                Ut.dtype() == torch::kBFloat16);
+    int E = B.size(0);
+    int N = check_gather(Xn, rows, E, I);
+    int C = Xn.size(1);
+    TORCH_CHECK(O == 1 || O == 3 || O == 5 || O == 7, "unsupported O ", O);
+    const int OP = opad_of((int)O);
+    TORCH_CHECK(Ut.dim() == 3 && Ut.size(0) == (int64_t)C * F && Ut.size(1) == E &&
+                Ut.size(2) == OP, "expect U as (C*F, E, OP(O))");
+    TORCH_CHECK(B.numel() == (int64_t)E * O * I * F);
+    TORCH_CHECK(C % UB_C == 0, "channels must be a multiple of 32");
+    TORCH_CHECK(O * I * F <= 343, "degree pair too large for LDS staging");
+    TORCH_CHECK(I <= 8, "I (2*d_in+1) must be <= 8");
+    if (E == 0) return;
+    auto stream = at::cuda::getCurrentHIPStream();
+    dim3 grid((E + UB_E - 1) / UB_E);
+    size_t lds = (size_t)UB_E * O * F * 8 * 2 + (size_t)UB_C * UB_E * 8 * 2;
+#define UB_LAUNCH_GFWD(OPV)                                                   \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(ubuild_gather_fwd_kernel<T, OPV>),     \
+                       grid, dim3(UB_NT), lds, stream, B.data_ptr<float>(),   \
+                       tptr<const T>(Xn), rows.data_ptr<int>(),               \
+                       tptr<__bf16>(Ut), E, N, C, (int)O, (int)I, (int)F)
+    DISPATCH_F32_BF16(Xn, __bf16, {
+        if (OP == 8) UB_LAUNCH_GFWD(8);
+        else if (OP == 4) UB_LAUNCH_GFWD(4);
+        else UB_LAUNCH_GFWD(1);
+    });
+#undef UB_LAUNCH_GFWD
+    check_launch("ubuild_gather_fwd: ");
+}
+
+void ubuild_gather_bwd_dx(torch::Tensor B, torch::Tensor dU, torch::Tensor rows,
+                          torch::Tensor dXn, int64_t O, int64_t I, int64_t F) {
+    TORCH_CHECK(B.is_cuda() && B.is_contiguous() && B.dtype() == torch::kFloat32);
+    TORCH_CHECK(dU.is_cuda() && dU.is_contiguous() &&
+                dU.dtype() == torch::kFloat32);
+    TORCH_CHECK(dXn.dtype() == torch::kFloat32,
+                "dXn accumulates in fp32 (zero it, cast afterwards)");
+    int E = B.size(0);
+    int N = check_gather(dXn, rows, E, I);
+    int C = dXn.size(1);
+    TORCH_CHECK(C % UB_C == 0, "channels must be a multiple of 32");
+    TORCH_CHECK(O * I * F <= 343);
+    TORCH_CHECK(O == 1 || O == 3 || O == 5 || O == 7, "unsupported O ", O);
+    TORCH_CHECK(B.numel() == (int64_t)E * O * I * F &&
+                dU.numel() == (int64_t)C * F * E * opad_of((int)O),
+                "expect dU as (C*F, E, OP(O))");
+    if (E == 0) return;
+    // channel chunk: one edge's run of chunk*I floats is >= 128 B; halved
+    // while B plus the dU tile would pass 64 KiB
+    int cb = I >= 5 ? 8 : (I >= 3 ? 16 : 32);
+    auto lds_of = [&](int c) {
+        return (size_t)UB_EB * O * I * F * 4 + (size_t)c * F * O * UB_EB * 4;
+    };
+    while (cb > 8 && lds_of(cb) > 64 * 1024) cb /= 2;
+    size_t lds = lds_of(cb);
+    TORCH_CHECK(lds + UB_EB * 4 <= 64 * 1024,
+                "degree pair too large for LDS staging");
+    auto stream = at::cuda::getCurrentHIPStream();
+    dim3 grid((E + UB_EB - 1) / UB_EB);
+#define UB_LAUNCH_GDX(CBV)                                                    \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(ubuild_gather_bwd_dx_kernel<CBV>),     \
+                       grid, dim3(UB_NT), lds, stream, B.data_ptr<float>(),   \
+                       dU.data_ptr<float>(), rows.data_ptr<int>(),            \
+                       dXn.data_ptr<float>(), E, N, C, (int)O, (int)I, (int)F)
+    if (cb == 32) UB_LAUNCH_GDX(32);
+    else if (cb == 16) UB_LAUNCH_GDX(16);
+    else UB_LAUNCH_GDX(8);
+#undef UB_LAUNCH_GDX
+    check_launch("ubuild_gather_bwd_dx: ");
+}
+
+void ubuild_gather_bwd_db(torch::Tensor Xn, torch::Tensor rows, torch::Tensor dU,
+                          torch::Tensor dB, int64_t O, int64_t I, int64_t F) {
+    TORCH_CHECK(dU.is_cuda() && dU.is_contiguous() &&
+                dU.dtype() == torch::kFloat32);
+    TORCH_CHECK(dB.is_cuda() && dB.is_contiguous() &&
+                dB.dtype() == torch::kFloat32);
+    TORCH_CHECK(dB.dim() == 4, "expect dB as (E, O, I, F)");
+    int E = dB.size(0);
+    int N = check_gather(Xn, rows, E, I);
+    int C = Xn.size(1);
+    TORCH_CHECK(O == 1 || O == 3 || O == 5 || O == 7, "unsupported O ", O);
+    TORCH_CHECK(dU.numel() == (int64_t)C * F * E * opad_of((int)O) &&
+                dB.numel() == (int64_t)E * O * I * F);
+    TORCH_CHECK(C % UB_CB == 0, "channels must be a multiple of 8");
+    TORCH_CHECK(O * I * F <= 343);
+    if (E == 0) return;
+    size_t lds = (size_t)UB_CB * UB_EB * (F * O + I) * 4;
+    TORCH_CHECK(lds <= 64 * 1024, "degree pair too large for LDS staging");
+    auto stream = at::cuda::getCurrentHIPStream();
+    dim3 grid((E + UB_EB - 1) / UB_EB);
+    DISPATCH_F32_BF16(Xn, __bf16, {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(ubuild_gather_bwd_db_kernel<T>), grid,
+                           dim3(UB_NT), lds, stream, tptr<const T>(Xn),
+                           rows.data_ptr<int>(), dU.data_ptr<float>(),
+                           dB.data_ptr<float>(), E, N, C, (int)O, (int)I, (int)F);
+    });
+    check_launch("ubuild_gather_bwd_db: ");
 }

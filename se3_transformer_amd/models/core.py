@@ -292,6 +292,35 @@ class PairwiseConv(nn.Module):
         out = torch.cat(outs, dim=0) if len(outs) > 1 else outs[0]
         return out.view(*lead, mo, O)
 
+    def fused_nodes_ok(self, basis, x_nodes):
+        """True when this pair takes apply_fused_nodes: the pairconv kernels
+        serve it and SE3_RECOMPUTE_U with the ubuild kernels holds."""
+        from ..ops import fused as _fused
+        O, I, F_ = self.d_out, to_order(self.degree_in), self.num_freq
+        if not _fused.switch_on('SE3_RECOMPUTE_U'):
+            return False
+        b = basis_entry(basis, self.degree_in, self.degree_out)
+        return (_fused.pairconv_ok(x_nodes, self.nc_out, self.nc_in * F_, O,
+                                   self.rp.mid_dim)
+                and _fused.recompute_u_ok(x_nodes, b, self.nc_in, O, I, F_))
+
+    def apply_fused_nodes(self, edge_feats, basis, x_nodes, rows):
+        """apply_fused on the features per node, x_nodes (b, n, mi, 2di+1),
+        and the row of every edge (fused.edge_rows) instead of the gathered
+        (b, n, k, mi, 2di+1) tensor, which is never built; u is rebuilt in
+        the backward instead of saved. Call only where fused_nodes_ok."""
+        from ..ops import fused as _fused
+        O, I, F_ = self.d_out, to_order(self.degree_in), self.num_freq
+        lead = edge_feats.shape[:-1]
+        ef = edge_feats.reshape(-1, edge_feats.shape[-1])
+        braw = basis_entry(basis, self.degree_in, self.degree_out) \
+            .reshape(ef.shape[0], O, I, F_).contiguous()
+        w6 = self.rp.net[6]
+        out = _fused.pairconv_from_nodes(
+            x_nodes.reshape(-1, self.nc_in, I), rows, braw,
+            self.rp.hidden(ef), w6.weight, w6.bias, self.nc_out, O, I, F_)
+        return out.view(*lead, self.nc_out, O).to(x_nodes.dtype)
+
 
 class ConvSE3(nn.Module):
     """Tensor-field-network convolution over neighbor edges (reference :154-268).
@@ -340,13 +369,32 @@ class ConvSE3(nn.Module):
             rel = fourier_encode(rel[..., None], num_encodings=self.num_fourier_features)
         edge_feats = torch.cat((rel, edges), dim=-1) if edges is not None else rel
 
-        # gather neighbor features once per input degree
+        pairs = list(self.fiber_in * self.fiber_out)
+        # SE3_RECOMPUTE_U: the pairs that qualify read the node features
+        # through the edge rows, computed once; no pair qualifies when off
+        from_nodes = {(di, do) for (di, _mi), (do, _mo) in pairs
+                      if self.kernel_unary[f'({di},{do})'].fused_nodes_ok(
+                          basis, inp[str(di)])}
+        rows = None
+        if from_nodes:
+            from ..ops.fused import edge_rows
+            rows = edge_rows(neighbor_indices, inp[str(pairs[0][0][0])].shape[1])
+
+        # gather neighbor features once per input degree that a pair still
+        # reads gathered
         gathered = {}
         for di, _ in self.fiber_in:
+            if all((di, do) in from_nodes for do, _ in self.fiber_out):
+                continue
             x = batched_index_select(inp[str(di)], neighbor_indices, dim=1)
             gathered[di] = x  # (b, n, k, mi, 2di+1)
 
-        pairs = list(self.fiber_in * self.fiber_out)
+        def run_pair(di, do):
+            pc = self.kernel_unary[f'({di},{do})']
+            if (di, do) in from_nodes:
+                return pc.apply_fused_nodes(edge_feats, basis, inp[str(di)], rows)
+            return pc.apply_fused(edge_feats, basis, gathered[di])
+
         # opt-in: overlaps independent pairs on a stream pool; capture with
         # forked streams hangs on ROCm 7.2, so single-stream loop mid-capture
         from ..ops.fused import switch_on
@@ -364,16 +412,14 @@ class ConvSE3(nn.Module):
                 s = pool[idx % len(pool)]
                 s.wait_stream(cur)
                 with torch.cuda.stream(s):
-                    pc = self.kernel_unary[f'({di},{do})']
-                    pair_out[(di, do)] = pc.apply_fused(edge_feats, basis, gathered[di])
+                    pair_out[(di, do)] = run_pair(di, do)
             for s in pool:
                 cur.wait_stream(s)
             for t in pair_out.values():
                 t.record_stream(cur)
         else:
             for (di, _mi), (do, _mo) in pairs:
-                pc = self.kernel_unary[f'({di},{do})']
-                pair_out[(di, do)] = pc.apply_fused(edge_feats, basis, gathered[di])
+                pair_out[(di, do)] = run_pair(di, do)
 
         outputs = {}
         for do, _mo in self.fiber_out:

@@ -37,6 +37,8 @@ SWITCHES = {
     'SE3_FORCE_FUSED': 'pairconv kernels also for fp32 input outside autocast',
     'SE3_TORCH_BWD': 'pairconv backward through library GEMMs (parity oracle)',
     'SE3_LOWMEM_PACK': 'save W unpacked and re-pack in the pairconv backward',
+    'SE3_RECOMPUTE_U': 'build U from node features and rebuild it in the '
+                       'pairconv backward',
     'SE3_COMPACT_NEIGHBORS': 'cut neighbor columns that are invalid in every row',
     'SE3_STREAMS': 'run the degree pairs of a ConvSE3 on a stream pool',
     'SE3_ATTN_MAX_J': 'largest neighbor count the attention kernel takes',
@@ -65,6 +67,7 @@ _ENTRY_POINTS = (
     'pairconv_fwd_opad', 'pairconv_opad', 'pairconv_bwd_dh', 'pairconv_bwd_dw',
     'pairconv_bwd_du', 'pack_w_both', 'pack_g', 'radial_trunk_fwd',
     'radial_trunk_bwd', 'ubuild_fwd', 'ubuild_bwd_dx', 'ubuild_bwd_db',
+    'ubuild_gather_fwd', 'ubuild_gather_bwd_dx', 'ubuild_gather_bwd_db',
     'sh_basis_fwd', 'sh_basis_bwd', 'knn_graph', 'knn_max_lds_bytes',
     'attn2_fwd', 'attn2_bwd', 'norm_se3_nl_fwd', 'norm_se3_nl_bwd',
     'norm_se3_gated_max_c', 'norm_se3_gated_fwd', 'norm_se3_gated_bwd',
@@ -182,6 +185,13 @@ def ubuild_ok(B, C, O, I, F) -> bool:
             and not switch_on('SE3_EAGER_UBUILD') and ext_available())
 
 
+def recompute_u_ok(x_nodes, B, C, O, I, F) -> bool:
+    """SE3_RECOMPUTE_U: the pair builds U from node features (N, C, I) and
+    edge rows, and builds it again in backward instead of saving it."""
+    return (x_nodes.is_cuda and x_nodes.dtype in _KERNEL_DTYPES
+            and switch_on('SE3_RECOMPUTE_U') and ubuild_ok(B, C, O, I, F))
+
+
 def pairconv_ok(x, mo: int, miF: int, O: int, mid_dim: int) -> bool:
     """bf16 compute: under autocast, for bf16 features, or SE3_FORCE_FUSED.
     The one gate that raises when the extension is missing on a GPU."""
@@ -272,139 +282,156 @@ class _FusedPairConvOpad(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, H, W, bias, U, mo, O):
-        ext = _load_ext()
-        E = H.shape[0]
-        miF, _, OP = U.shape
-        H16 = H.contiguous().to(torch.bfloat16)
         U16 = U.contiguous().to(torch.bfloat16)
-        # bias term: out0[e,mo,o] = sum_c bias[mo,c] U[c,e,o]
-        b16 = bias.detach().to(torch.bfloat16).view(mo, miF)
-        out = (b16 @ U16.view(miF, E * OP)).view(mo, E, OP)[:, :, :O] \
-            .permute(1, 0, 2).contiguous().float()
-        hip_bwd = not switch_on('SE3_TORCH_BWD')
-        # SE3_LOWMEM_PACK=1 trades ~6% step time for memory: save the
-        # torch-layout bf16 W (1x) and re-pack in backward, instead of
-        # holding both packed fragment layouts (2x) through autograd —
-        # frees ~36 GB at the headline 18.2B-param config (enables larger
-        # neighbor counts before the activation-memory wall).
-        lowmem = switch_on('SE3_LOWMEM_PACK')
-        if hip_bwd and not lowmem:
-            # one-pass pack kernel: W read once, both fragment layouts
-            # written; saved for backward so nothing re-packs per step
-            Wd = W.detach().contiguous()
-            n128 = mo * miF * 128
-            Pf = torch.empty(n128, dtype=torch.bfloat16, device=Wd.device)
-            Pdh = torch.empty(n128, dtype=torch.bfloat16, device=Wd.device)
-            ext.pack_w_both(Wd, Pf, Pdh, mo)
-            ext.pairconv_fwd_opad(H16, Pf, U16, out, mo)
-            ctx.save_for_backward(H16, Pf, Pdh, U16, b16)
-            ctx.packed = True
-        else:
-            W16 = W.detach().contiguous().to(torch.bfloat16)
-            ext.pairconv_fwd_opad(H16, _pack_w_fwd(W16, mo, miF), U16, out, mo)
-            ctx.save_for_backward(H16, W16, U16, b16)
-            ctx.packed = False
-        ctx.mo = mo
-        ctx.O = O
-        ctx.w_dtype = W.dtype
-        ctx.b_dtype = bias.dtype
+        out, H16, wsave, b16 = _pairconv_forward(ctx, H, W, bias, U16, mo, O)
+        ctx.save_for_backward(H16, *wsave, U16, b16)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        mo, O = ctx.mo, ctx.O
-        if ctx.packed:
-            H16, Pf, Pdh, U16, b16 = ctx.saved_tensors
-        else:
-            H16, W16, U16, b16 = ctx.saved_tensors
-        E, K = H16.shape
-        miF, _, OP = U16.shape
-        g = grad_out.contiguous().float()              # (E, mo, O) fp32
+        H16, *wsave, U16, b16 = ctx.saved_tensors
+        return (*_pairconv_backward(ctx, H16, wsave, b16, U16, grad_out,
+                                    ctx.needs_input_grad[:4]), None, None)
 
-        need_H, need_W, need_b, need_u = ctx.needs_input_grad[:4]
 
-        ext = _load_ext()
-        if not switch_on('SE3_TORCH_BWD'):
-            dH = dW = db = dU = None
-            # one pass: cast, transpose and pad, (mo, E, OP) bf16
-            G = torch.empty(mo, E, OP, dtype=torch.bfloat16, device=g.device)
-            ext.pack_g(g, G)
-            P1 = Pu = None
-            if ctx.packed:
-                P1, Pu = Pdh, Pf
-            elif need_H or need_u:
-                # SE3_LOWMEM_PACK path: re-derive both fragment layouts in
-                # one kernel pass from the saved torch-layout W
-                n128 = mo * miF * K
-                Pu = torch.empty(n128, dtype=torch.bfloat16,
-                                 device=H16.device)
-                P1 = torch.empty_like(Pu)
-                ext.pack_w_both(W16, Pu, P1, mo)
-            if need_H:
-                dH = torch.zeros(E, K, dtype=torch.float32, device=H16.device)
-                ext.pairconv_bwd_dh(G, U16, P1, dH, mo, O)
-            P1 = None
-            if need_W:
-                Ht = H16.t().contiguous()              # (128, E)
-                dW = torch.empty(mo * miF, K, dtype=torch.float32,
-                                 device=H16.device)
-                ext.pairconv_bwd_dw(G, U16, Ht, dW, mo, O)
-                dW = dW.to(ctx.w_dtype)
-                del Ht
-            if need_b:
-                # db[(m,c)] = sum_{e,o} g[m,e,o] u[c,e,o] — one GEMM, both
-                # operands are free (mo,E*OP)/(miF,E*OP) views
-                db = (G.view(mo, E * OP) @ U16.view(miF, E * OP).t()) \
-                    .reshape(mo * miF).to(ctx.b_dtype)
-            if need_u:
-                dU = torch.empty(miF, E, OP, dtype=torch.float32,
-                                 device=H16.device)
-                ext.pairconv_bwd_du(H16, Pu, b16.float().reshape(-1),
-                                    G, dU, mo, O)
-            return dH, dW, db, dU, None, None
+def _pairconv_forward(ctx, H, W, bias, U16, mo, O):
+    """The forward of both pairconv Functions on U16 (miF, E, OP) bf16.
+    Returns out and what the backward needs besides U: H16, wsave (both
+    fragment packs of W, or W16 alone: ctx.packed says which) and b16."""
+    ext = _load_ext()
+    E = H.shape[0]
+    miF, _, OP = U16.shape
+    H16 = H.contiguous().to(torch.bfloat16)
+    # bias term: out0[e,mo,o] = sum_c bias[mo,c] U[c,e,o]
+    b16 = bias.detach().to(torch.bfloat16).view(mo, miF)
+    out = (b16 @ U16.view(miF, E * OP)).view(mo, E, OP)[:, :, :O] \
+        .permute(1, 0, 2).contiguous().float()
+    hip_bwd = not switch_on('SE3_TORCH_BWD')
+    # SE3_LOWMEM_PACK=1 trades ~6% step time for memory: save the
+    # torch-layout bf16 W (1x) and re-pack in backward, instead of
+    # holding both packed fragment layouts (2x) through autograd —
+    # frees ~36 GB at the headline 18.2B-param config (enables larger
+    # neighbor counts before the activation-memory wall).
+    lowmem = switch_on('SE3_LOWMEM_PACK')
+    if hip_bwd and not lowmem:
+        # one-pass pack kernel: W read once, both fragment layouts
+        # written; saved for backward so nothing re-packs per step
+        Wd = W.detach().contiguous()
+        n128 = mo * miF * 128
+        Pf = torch.empty(n128, dtype=torch.bfloat16, device=Wd.device)
+        Pdh = torch.empty(n128, dtype=torch.bfloat16, device=Wd.device)
+        ext.pack_w_both(Wd, Pf, Pdh, mo)
+        ext.pairconv_fwd_opad(H16, Pf, U16, out, mo)
+        wsave = (Pf, Pdh)
+        ctx.packed = True
+    else:
+        W16 = W.detach().contiguous().to(torch.bfloat16)
+        ext.pairconv_fwd_opad(H16, _pack_w_fwd(W16, mo, miF), U16, out, mo)
+        wsave = (W16,)
+        ctx.packed = False
+    ctx.mo = mo
+    ctx.O = O
+    ctx.w_dtype = W.dtype
+    ctx.b_dtype = bias.dtype
+    return out, H16, wsave, b16
 
-        if ctx.packed:   # pragma: no cover - env toggled between fwd and bwd
-            raise RuntimeError('SE3_TORCH_BWD enabled after a packed forward; '
-                               'set it before the forward pass')
-        g16 = g.to(torch.bfloat16)
-        u_eco = U16[:, :, :O].permute(1, 0, 2)         # (E, miF, O) view
+
+def _pairconv_backward(ctx, H16, wsave, b16, U16, grad_out, needs):
+    """The backward of both pairconv Functions on U16, saved or rebuilt:
+    (dH, dW, db, dU) for needs = (need_H, need_W, need_b, need_u)."""
+    mo, O = ctx.mo, ctx.O
+    if ctx.packed:
+        Pf, Pdh = wsave
+    else:
+        W16, = wsave
+    E, K = H16.shape
+    miF, _, OP = U16.shape
+    g = grad_out.contiguous().float()              # (E, mo, O) fp32
+
+    need_H, need_W, need_b, need_u = needs
+
+    ext = _load_ext()
+    if not switch_on('SE3_TORCH_BWD'):
         dH = dW = db = dU = None
+        # one pass: cast, transpose and pad, (mo, E, OP) bf16
+        G = torch.empty(mo, E, OP, dtype=torch.bfloat16, device=g.device)
+        ext.pack_g(g, G)
+        P1 = Pu = None
+        if ctx.packed:
+            P1, Pu = Pdh, Pf
+        elif need_H or need_u:
+            # SE3_LOWMEM_PACK path: re-derive both fragment layouts in
+            # one kernel pass from the saved torch-layout W
+            n128 = mo * miF * K
+            Pu = torch.empty(n128, dtype=torch.bfloat16,
+                             device=H16.device)
+            P1 = torch.empty_like(Pu)
+            ext.pack_w_both(W16, Pu, P1, mo)
         if need_H:
             dH = torch.zeros(E, K, dtype=torch.float32, device=H16.device)
+            ext.pairconv_bwd_dh(G, U16, P1, dH, mo, O)
+        P1 = None
         if need_W:
-            dW = torch.empty(mo * miF, K, dtype=torch.float32, device=H16.device)
-        if need_b:
-            db = torch.empty(mo * miF, dtype=torch.float32, device=H16.device)
-        if need_u:
-            dU = torch.zeros(miF, E, OP, dtype=torch.float32, device=H16.device)
-
-        # chunk over mo so the dR slab stays ~<= 1 GiB
-        per_mo = E * miF * 2
-        cm = max(8, min(mo, (1 << 30) // max(per_mo, 1) // 8 * 8))
-        for m0 in range(0, mo, cm):
-            m1 = min(mo, m0 + cm)
-            # dR[e,(m,c)] = sum_o g[e,m,o] * u[e,c,o]
-            dR16 = torch.einsum('emo,eco->emc', g16[:, m0:m1], u_eco) \
-                .reshape(E, (m1 - m0) * miF)
-            Wslab = W16[m0 * miF:m1 * miF]             # ((m1-m0)*miF, K)
-            if need_H:
-                dH += (dR16 @ Wslab).float()
-            if need_W:
-                dW[m0 * miF:m1 * miF] = (dR16.t() @ H16).float()
-            if need_b:
-                db[m0 * miF:m1 * miF] = dR16.float().sum(dim=0)
-            if need_u:
-                # R[e,(m,c)] = H @ W^T + bias ; du[c,e,o] += sum_m R * g
-                R = (H16 @ Wslab.t()).view(E, m1 - m0, miF).float() \
-                    + b16[m0:m1].float().unsqueeze(0)
-                dU[:, :, :O] += torch.einsum('emc,emo->ceo', R, g[:, m0:m1])
-            del dR16
-
-        if need_W:
+            Ht = H16.t().contiguous()              # (128, E)
+            dW = torch.empty(mo * miF, K, dtype=torch.float32,
+                             device=H16.device)
+            ext.pairconv_bwd_dw(G, U16, Ht, dW, mo, O)
             dW = dW.to(ctx.w_dtype)
+            del Ht
         if need_b:
-            db = db.to(ctx.b_dtype)
-        return dH, dW, db, dU, None, None
+            # db[(m,c)] = sum_{e,o} g[m,e,o] u[c,e,o] — one GEMM, both
+            # operands are free (mo,E*OP)/(miF,E*OP) views
+            db = (G.view(mo, E * OP) @ U16.view(miF, E * OP).t()) \
+                .reshape(mo * miF).to(ctx.b_dtype)
+        if need_u:
+            dU = torch.empty(miF, E, OP, dtype=torch.float32,
+                             device=H16.device)
+            ext.pairconv_bwd_du(H16, Pu, b16.float().reshape(-1),
+                                G, dU, mo, O)
+        return dH, dW, db, dU
+
+    if ctx.packed:   # pragma: no cover - env toggled between fwd and bwd
+        raise RuntimeError('SE3_TORCH_BWD enabled after a packed forward; '
+                           'set it before the forward pass')
+    g16 = g.to(torch.bfloat16)
+    u_eco = U16[:, :, :O].permute(1, 0, 2)         # (E, miF, O) view
+    dH = dW = db = dU = None
+    if need_H:
+        dH = torch.zeros(E, K, dtype=torch.float32, device=H16.device)
+    if need_W:
+        dW = torch.empty(mo * miF, K, dtype=torch.float32, device=H16.device)
+    if need_b:
+        db = torch.empty(mo * miF, dtype=torch.float32, device=H16.device)
+    if need_u:
+        dU = torch.zeros(miF, E, OP, dtype=torch.float32, device=H16.device)
+
+    # chunk over mo so the dR slab stays ~<= 1 GiB
+    per_mo = E * miF * 2
+    cm = max(8, min(mo, (1 << 30) // max(per_mo, 1) // 8 * 8))
+    for m0 in range(0, mo, cm):
+        m1 = min(mo, m0 + cm)
+        # dR[e,(m,c)] = sum_o g[e,m,o] * u[e,c,o]
+        dR16 = torch.einsum('emo,eco->emc', g16[:, m0:m1], u_eco) \
+            .reshape(E, (m1 - m0) * miF)
+        Wslab = W16[m0 * miF:m1 * miF]             # ((m1-m0)*miF, K)
+        if need_H:
+            dH += (dR16 @ Wslab).float()
+        if need_W:
+            dW[m0 * miF:m1 * miF] = (dR16.t() @ H16).float()
+        if need_b:
+            db[m0 * miF:m1 * miF] = dR16.float().sum(dim=0)
+        if need_u:
+            # R[e,(m,c)] = H @ W^T + bias ; du[c,e,o] += sum_m R * g
+            R = (H16 @ Wslab.t()).view(E, m1 - m0, miF).float() \
+                + b16[m0:m1].float().unsqueeze(0)
+            dU[:, :, :O] += torch.einsum('emc,emo->ceo', R, g[:, m0:m1])
+        del dR16
+
+    if need_W:
+        dW = dW.to(ctx.w_dtype)
+    if need_b:
+        db = db.to(ctx.b_dtype)
+    return dH, dW, db, dU
 
 
 def fused_pairconv_opad(H, W, bias, U, mo, O=None):
@@ -617,6 +644,76 @@ def ubuild_opad(x, B, O, I, F):
 def ubuild(x, B, O, I, F):
     """The e-contiguous (C*F, O, E) contract, as a view of ubuild_opad."""
     return ubuild_opad(x, B, O, I, F)[:, :, :O].permute(0, 2, 1)
+
+
+def edge_rows(neighbor_indices, n: int):
+    """(b, n', k) neighbor indices into n nodes per batch -> (b*n'*k,) int32
+    rows batch*n + index of the features flattened to (b*n, C, I)."""
+    b = neighbor_indices.shape[0]
+    base = torch.arange(b, device=neighbor_indices.device).view(b, 1, 1) * n
+    return (neighbor_indices + base).reshape(-1).to(torch.int32).contiguous()
+
+
+class _PairConvNodesFn(torch.autograd.Function):
+    """ubuild and pairconv of one degree pair in one node, on the features
+    per NODE (SE3_RECOMPUTE_U): out = _FusedPairConvOpad(H, W, bias, U) with
+    U = ubuild(Xn[rows], B), the same bits, but U is a temporary of the
+    forward and is built again in the backward. Saved instead: Xn (N, C, I),
+    rows (E,) int32 and B. Neither the gathered features (E, C, I) nor their
+    gradient exist: dXn (N, C, I) is summed in fp32 by atomic adds and cast
+    once. dB comes back when the basis requires grad. First order only."""
+
+    @staticmethod
+    def forward(ctx, Xn, rows, B, H, W, bias, mo, O, I, F):
+        Xc = Xn.contiguous()
+        U16 = _PairConvNodesFn._build_u(Xc, rows, B, O, I, F)
+        out, H16, wsave, b16 = _pairconv_forward(ctx, H, W, bias, U16, mo, O)
+        ctx.save_for_backward(Xc, rows, B, H16, *wsave, b16)
+        ctx.IF = (I, F)
+        return out
+
+    @staticmethod
+    def _build_u(Xc, rows, B, O, I, F):
+        U16 = torch.empty(Xc.shape[1] * F, rows.shape[0], opad(O),
+                          dtype=torch.bfloat16, device=Xc.device)
+        _load_ext().ubuild_gather_fwd(B, Xc, rows, U16, O, I, F)
+        return U16
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        ext = _load_ext()
+        Xc, rows, B, H16, *wsave, b16 = ctx.saved_tensors
+        O, (I, F) = ctx.O, ctx.IF
+        need_X, _, need_B, need_H, need_W, need_b = ctx.needs_input_grad[:6]
+        dH, dW, db, dU = _pairconv_backward(
+            ctx, H16, wsave, b16,
+            _PairConvNodesFn._build_u(Xc, rows, B, O, I, F), grad_out,
+            (need_H, need_W, need_b, need_X or need_B))
+        dXn = dB = None
+        if dU is not None:
+            # between _FusedPairConvOpad and _UBuildFn autograd casts dU to
+            # the dtype of U, bf16: the same rounding here keeps dXn and dB
+            # those of the unfused path
+            dU = dU.to(torch.bfloat16).float()
+        if need_X:
+            # zeroed here, inside whatever graph captures the backward
+            dXn = torch.zeros(Xc.shape, dtype=torch.float32, device=Xc.device)
+            ext.ubuild_gather_bwd_dx(B, dU, rows, dXn, O, I, F)
+            dXn = dXn.to(Xc.dtype)
+        if need_B:
+            dB = torch.empty(B.shape, dtype=torch.float32, device=B.device)
+            ext.ubuild_gather_bwd_db(Xc, rows, dU, dB, O, I, F)
+        return dXn, None, dB, dH, dW, db, None, None, None, None
+
+
+def pairconv_from_nodes(Xn, rows, B, H, W, bias, mo, O, I, F):
+    """fused_pairconv_opad(H, W, bias, ubuild_opad(Xn[rows], B, O, I, F),
+    mo, O) without saving U or gathering Xn: Xn (N, C, I) fp32/bf16, rows
+    (E,) int32 in [0, N), B (E, O, I, F) fp32 contiguous. Returns (E, mo, O).
+    The kernels do not fault on a row outside [0, N): they read its x as zero
+    and drop its gradient, so a wrong index shows as a wrong result only."""
+    return _PairConvNodesFn.apply(Xn, rows, B, H, W, bias, mo, O, I, F)
 
 
 class _HtypeRelDistFn(torch.autograd.Function):
