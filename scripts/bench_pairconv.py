@@ -4,6 +4,8 @@ Usage (GPU box):  python scripts/bench_pairconv.py [--pair 3,3]
 Prints per-kernel ms and GEMM-equivalent TFLOP/s for fwd, bwd_dh, bwd_dw,
 bwd_du on the o-padded edge-major tensors U (miF, E, OP) / G (mo, E, OP), and
 the times of their two producers, ubuild_fwd and pack_g, separately.
+bwd_dw is timed with and without db; --du-dtype picks the dU that bwd_du
+writes (bf16 is what training uses, f32 what it wrote before).
 """
 import argparse
 import os
@@ -33,6 +35,7 @@ def main():
     p.add_argument('--E', type=int, default=9216)
     p.add_argument('--ch', type=int, default=512)
     p.add_argument('--only', default=None, choices=['fwd','dh','dw','du'])
+    p.add_argument('--du-dtype', default='bf16', choices=['bf16', 'f32'])
     args = p.parse_args()
     di, do = map(int, args.pair.split(','))
     F = 2 * min(di, do) + 1
@@ -42,6 +45,7 @@ def main():
     E, K = args.E, 128
     N = mo * miF
     dev = 'cuda'
+    du_dtype = {'bf16': torch.bfloat16, 'f32': torch.float32}[args.du_dtype]
     g = torch.Generator(device=dev).manual_seed(0)
 
     H = torch.randn(E, K, generator=g, device=dev).to(torch.bfloat16)
@@ -79,9 +83,11 @@ def main():
               'dh': lambda: _C.pairconv_bwd_dh(G, U, _pack_w_dh(W, mo, miF),
                                                torch.zeros(E, K, device=dev), mo, O),
               'dw': lambda: _C.pairconv_bwd_dw(G, U, H.t().contiguous(),
-                                               torch.empty(N, K, device=dev), mo, O),
+                                               torch.empty(N, K, device=dev),
+                                               torch.empty(N, device=dev), mo, O),
               'du': lambda: _C.pairconv_bwd_du(H, P, bias, G,
-                                               torch.empty(miF, E, OP, device=dev),
+                                               torch.empty(miF, E, OP, device=dev,
+                                                           dtype=du_dtype),
                                                mo, O)}[args.only]
         print(args.only, timeit(fn, iters=3, warmup=1), 'ms')
         return
@@ -114,12 +120,19 @@ def main():
 
     Ht = H.t().contiguous()
     dW = torch.empty(N, K, device=dev)
-    ms = timeit(lambda: _C.pairconv_bwd_dw(G, U, Ht, dW, mo, O))
+    no_db = torch.empty(0, device=dev)
+    ms = timeit(lambda: _C.pairconv_bwd_dw(G, U, Ht, dW, no_db, mo, O))
     print(f'bwd_dw ({di},{do}): {ms:8.3f} ms  {gemm_fl/ms/1e9:7.1f} TF/s')
+    db = torch.empty(N, device=dev)
+    ms = timeit(lambda: _C.pairconv_bwd_dw(G, U, Ht, dW, db, mo, O))
+    print(f'bwd_dw+db ({di},{do}): {ms:8.3f} ms  {gemm_fl/ms/1e9:7.1f} TF/s')
+    ms = timeit(lambda: G.view(mo, E * OP) @ U.view(miF, E * OP).t())
+    print(f'db as a library GEMM ({di},{do}): {ms:8.3f} ms')
 
-    dU = torch.empty(miF, E, OP, device=dev)
+    dU = torch.empty(miF, E, OP, device=dev, dtype=du_dtype)
     ms = timeit(lambda: _C.pairconv_bwd_du(H, P, bias, G, dU, mo, O))
-    print(f'bwd_du ({di},{do}): {ms:8.3f} ms  {gemm_fl/ms/1e9:7.1f} TF/s')
+    print(f'bwd_du ({di},{do}) {args.du_dtype}: {ms:8.3f} ms  '
+          f'{gemm_fl/ms/1e9:7.1f} TF/s')
 
     # library GEMM reference: the raw R = H @ W^T (what eager must do, without
     # even the contraction), on a slab 1/8 of N to fit memory

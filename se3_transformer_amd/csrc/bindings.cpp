@@ -8,8 +8,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     OP(pairconv_opad, "padded o width OP(O)");
     OP(pack_g, "grad_out (E, mo, O) f32 -> G (mo, E, OP) bf16, zero pads");
     OP(pairconv_bwd_dh, "dH backward");
-    OP(pairconv_bwd_dw, "dW backward");
-    OP(pairconv_bwd_du, "dU backward");
+    OP(pairconv_bwd_dw, "dW backward; also fills db (mo*miF,) f32 unless db is empty");
+    OP(pairconv_bwd_du, "dU backward, dU (miF, E, OP) bf16 or f32");
     OP(knn_graph, "on-device kNN graph build");
     OP(knn_max_lds_bytes, "dynamic-LDS ceiling of the kNN kernel (bounds n and k)");
     OP(attn2_fwd, "fused neighbor attention fwd (online softmax, in-kernel rotary)");

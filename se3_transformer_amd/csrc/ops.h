@@ -10,7 +10,8 @@ using torch::Tensor;
 int64_t pairconv_opad(int64_t O);
 void pairconv_fwd_opad(Tensor H, Tensor W, Tensor Ut, Tensor out, int64_t mo_);
 void pairconv_bwd_dh(Tensor G, Tensor U, Tensor Wt, Tensor dH, int64_t mo_, int64_t O_);
-void pairconv_bwd_dw(Tensor G, Tensor U, Tensor Ht, Tensor dW, int64_t mo_, int64_t O_);
+void pairconv_bwd_dw(Tensor G, Tensor U, Tensor Ht, Tensor dW, Tensor db, int64_t mo_,
+                     int64_t O_);
 void pairconv_bwd_du(Tensor H, Tensor W, Tensor bias, Tensor G, Tensor dU,
                      int64_t mo_, int64_t O_);
 void pack_w_both(Tensor W, Tensor Pf, Tensor Pdh, int64_t mo_);

@@ -4,7 +4,7 @@
 //   out[e,mo,o] = sum_c R[e,(mo,c)] * u[c,e,o]
 //
 // u, g and du are o-padded and edge-major (OP = opad_of(O), pads zero):
-//   U (miF, E, OP) bf16 | G (mo, E, OP) bf16 (pack_g) | dU (miF, E, OP) f32
+//   U (miF, E, OP) bf16 | G (mo, E, OP) bf16 (pack_g) | dU (miF, E, OP) bf16 or f32
 // so every kernel stages whole (row, edge) vectors with plain copies. At
 // O=1 that layout is the [row][E] the kernels always read, and the O=1
 // instantiations stage as they always did.
@@ -13,7 +13,7 @@
 //   dR[e,n]   = sum_o g[mo,e,o] * u[c,e,o]          (v_dot2, recomputed on the fly)
 //   dH[e,k]   = sum_n dR[e,n] * W[n,k]              (kernel B1, MFMA, needs W^T)
 //   dW[n,k]   = sum_e dR[e,n] * H[e,k]              (kernel B2, MFMA, needs H^T)
-//   db[n]     = sum_e dR[e,n]                       (one library GEMM over G and U, ops/fused.py)
+//   db[n]     = sum_e dR[e,n]                       (kernel B2, f32 sums of its dR entries)
 //   du[c,e,o] = sum_mo R[e,(mo,c)] * g[mo,e,o]      (kernel B3, recomputes R)
 //
 // dR / R are never written to global memory anywhere.
@@ -232,6 +232,21 @@ __device__ __forceinline__ void dw_write_tile(float* __restrict__ dW, const f32x
             }
 }
 
+// db[n] = sum_e dR[e,n] of the tile's rows n = (m, uc), m < 4: s[m] is this
+// thread's sum over its e-pair of every chunk; the 16 threads of one uc are
+// consecutive lanes. The block owns its rows, so the store is exclusive.
+__device__ __forceinline__ void dw_write_db(float* __restrict__ db, const float (&s)[4],
+                                            int mb, int cb, int miF, int tid) {
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        float v = s[m];
+#pragma unroll
+        for (int d = 8; d >= 1; d >>= 1) v += __shfl_xor(v, d, 16);
+        if ((tid & 15) == 0)
+            db[(size_t)(mb * 4 + m) * miF + cb * 32 + (tid >> 4)] = v;
+    }
+}
+
 // ---------------------------------------------------------------------------
 // B2: dW[n,k] = sum_e dR[e,n] H[e,k];  db[n] = sum_e dR[e,n]
 // block: n-tile 128 (4 mo x 32 urow) x 128 k, loops e in chunks of 32.
@@ -244,13 +259,16 @@ __device__ __forceinline__ void dw_write_tile(float* __restrict__ dW, const f32x
 // thread, stored as four 4-byte e-pairs into the [128 n][32 e] MFMA image
 // (a wave's stores cover 4 whole 64 B rows: conflict-free). Only the
 // 4 x 32 g vectors and the H^T tile are staged in LDS.
+// With DB the thread also sums its f32 dR entries, before their bf16
+// rounding, into db (dw_write_db); without it the kernel is what it was.
 // ---------------------------------------------------------------------------
-template <int O>
+template <int O, bool DB>
 __global__ void __launch_bounds__(NT)
 pairconv_bwd_dw_kernel(const __bf16* __restrict__ Gt,  // (mo, E, OP)
                        const __bf16* __restrict__ Ut,  // (miF, E, OP)
                        const __bf16* __restrict__ Ht,  // (128, E)
                        float* __restrict__ dW,         // (mo*miF, 128) f32
+                       float* __restrict__ db,         // (mo*miF,) f32, DB only
                        int E, int mo, int miF) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int OP = opad_of(O);
@@ -293,6 +311,7 @@ pairconv_bwd_dw_kernel(const __bf16* __restrict__ Gt,  // (mo, E, OP)
         h_reg = dw_load_h(Ht, E, e0, tid);
     };
 
+    float dbs[4] = {0.f, 0.f, 0.f, 0.f};
     load_chunk(0);
     for (int ec = 0; ec < nec; ++ec) {
         __syncthreads();   // previous MFMA done reading the LDS images
@@ -310,27 +329,33 @@ pairconv_bwd_dw_kernel(const __bf16* __restrict__ Gt,  // (mo, E, OP)
         for (int m = 0; m < 4; ++m) {
             ovec g0 = *reinterpret_cast<const ovec*>(g_lds + (size_t)(m * 32 + ue) * OP);
             ovec g1 = *reinterpret_cast<const ovec*>(g_lds + (size_t)(m * 32 + ue + 1) * OP);
+            const float d0 = dot_ovec<OP>(g0, u0), d1 = dot_ovec<OP>(g1, u1);
+            if constexpr (DB) dbs[m] += d0 + d1;
             *reinterpret_cast<bf16x2*>(dr_lds + (size_t)(m * 32 + uc) * 32 + ue) =
-                bf16x2{(__bf16)dot_ovec<OP>(g0, u0), (__bf16)dot_ovec<OP>(g1, u1)};
+                bf16x2{(__bf16)d0, (__bf16)d1};
         }
         __syncthreads();
         dw_mfma_chunk(acc, dr_lds, h_lds, wn, wk, l15, l4);
     }
     __syncthreads();
     dw_write_tile(dW, acc, mb, cb, miF, wn, wk, l15, l4);
+    if constexpr (DB) dw_write_db(db, dbs, mb, cb, miF, tid);
 }
 
 // ---------------------------------------------------------------------------
 // B2 at O=1: G and U are plain [row][E] (the padded layout with OP=1), there
 // is no o to contract, and a dR entry is one product. The tile, the staging
 // pipeline and the MFMA step are those of the kernel above; dR^T is built
-// from LDS images of the g and u rows, as e-pairs.
+// from LDS images of the g and u rows, as e-pairs: pass j of a thread is
+// row (m = j, c = tid >> 4), the same (uc, e-pair) ownership, so db sums alike.
 // ---------------------------------------------------------------------------
+template <bool DB>
 __global__ void __launch_bounds__(NT)
 pairconv_bwd_dw_o1_kernel(const __bf16* __restrict__ Gt,  // (mo, E)
                           const __bf16* __restrict__ Ut,  // (miF, E)
                           const __bf16* __restrict__ Ht,  // (128, E)
                           float* __restrict__ dW,         // (mo*miF, 128) f32
+                          float* __restrict__ db,         // (mo*miF,) f32, DB only
                           int E, int mo, int miF) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     __bf16* dr_lds = reinterpret_cast<__bf16*>(smem);                  // [128n][32e] 8 KiB
@@ -372,6 +397,7 @@ pairconv_bwd_dw_o1_kernel(const __bf16* __restrict__ Gt,  // (mo, E)
         h_reg = dw_load_h(Ht, E, e0, tid);
     };
 
+    float dbs[4] = {0.f, 0.f, 0.f, 0.f};
     load_chunk(0);
     for (int ec = 0; ec < nec; ++ec) {
         __syncthreads();   // previous MFMA done reading the LDS images
@@ -384,58 +410,144 @@ pairconv_bwd_dw_o1_kernel(const __bf16* __restrict__ Gt,  // (mo, E)
         if (ec + 1 < nec) load_chunk(ec + 1);   // issue next loads early
         __syncthreads();
         // cooperative dR^T tile [128n][32e] (e-pairs, packed)
-        for (int i = tid; i < (128 * 32) / 2; i += NT) {
+        static_assert((128 * 32) / 2 == 4 * NT, "db: pass j is mo j");
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            int i = tid + j * NT;
             int e = (i & 15) * 2, n = i >> 4;
             int m = n >> 5, c = n & 31;
             f32x2 gv = b2f2(*reinterpret_cast<const bf16x2*>(g_lds + m * 32 + e));
             f32x2 uv = b2f2(*reinterpret_cast<const bf16x2*>(u_lds + c * 32 + e));
+            const float d0 = fmaf(gv[0], uv[0], 0.f), d1 = fmaf(gv[1], uv[1], 0.f);
+            if constexpr (DB) dbs[j] += d0 + d1;
             *reinterpret_cast<bf16x2*>(dr_lds + (size_t)n * 32 + e) =
-                bf16x2{(__bf16)fmaf(gv[0], uv[0], 0.f), (__bf16)fmaf(gv[1], uv[1], 0.f)};
+                bf16x2{(__bf16)d0, (__bf16)d1};
         }
         __syncthreads();
         dw_mfma_chunk(acc, dr_lds, h_lds, wn, wk, l15, l4);
     }
     __syncthreads();
     dw_write_tile(dW, acc, mb, cb, miF, wn, wk, l15, l4);
+    if constexpr (DB) dw_write_db(db, dbs, mb, cb, miF, tid);
 }
 
 // ---------------------------------------------------------------------------
 // B3: du[c,e,o] = sum_mo R[e,(mo,c)] g[mo,e,o],  R = H @ W^T + bias
-// G is read as (mo, E, OP) vectors and dU written as (miF, E, OP) vectors;
-// inside, the tiles keep e on the lanes.
+// G is read as (mo, E, OP) vectors and dU written as (miF, E, OP) vectors,
+// f32 or bf16 (TD; the bf16 form rounds the f32 sums once, to nearest even).
 // block: 64 e x 32 urow, loops mo in blocks of 8; the R tile is recomputed by
 // the forward's MFMA loop (mfma_rtile), bounced through LDS, contracted vs g.
+//
+// A thread owns the cells (e = lane, c = 4 wid + k), k < 4, for the whole
+// kernel and keeps their 4 x O sums in registers: LDS holds only h | R | g |
+// bias, 68,608 B at OP = 8, so two workgroups are resident on a CU at every
+// O and one block's W-fragment loads and MFMA phase overlap the other's
+// bounce and contraction. With the f32 sums in LDS (41 KB at O = 5, 57 KB at
+// O = 7) the launch asked for 96-115 KB and ran one workgroup per CU at
+// O >= 5, every phase serialised by the barriers; that, not the layout, was
+// the 4-10 % that du lost against the e-contiguous kernel
+// (profiles/du_residency.md).
+//
+// The R bounce is [e][q][m][k] (n = (m, c = 4 q + k)), rows DU_RP apart: the
+// four registers of an MFMA fragment are the four k of one (e, q, m), one
+// 8-byte store, and the 32 values a thread contracts are 64 contiguous
+// bytes of its row, four 16-byte reads. DU_RP = 264 elements = 132 dwords
+// keeps those reads conflict-free (16 lanes x 4 banks tile the 64 banks).
+// The g tile sits [m][e][OP] as in memory: per m a thread reads one vector,
+// widens it once and uses it for its four cells. g and bias are double
+// buffered, so a mo-block needs two barriers, not three.
 // No W prefetch here: the contraction phase holds more live state than the
 // forward's epilogue, and prefetching under the 2-blocks/CU cap spilled
 // 116-240 B/lane (profiles/LADDER.md).
 // ---------------------------------------------------------------------------
-template <int O>
+#define DU_RP 264   // R bounce row pitch, elements
+
+// mfma_rtile for du, same MFMA order and so the same R bits, with the W
+// fragments in a ring of two k-steps: step kit+2 loads when step kit's MFMAs
+// are issued, and nothing crosses a step. Left to itself the compiler fills
+// what the du sums leave of the 128 registers with W loads hoisted as far as
+// they go and then spills at O = 7; this holds 32.
+__device__ __forceinline__ void du_rtile(f32x4 (&acc)[4][2], const __bf16* h_lds,
+                                         const __bf16* pbase, int we, int l15, int l4) {
+#pragma unroll
+    for (int mf = 0; mf < 4; ++mf)
+#pragma unroll
+        for (int ef = 0; ef < 2; ++ef) acc[mf][ef] = f32x4(0.f);
+    bf16x8 a[2][4];
+#pragma unroll
+    for (int kit = 0; kit < 2; ++kit)
+#pragma unroll
+        for (int mf = 0; mf < 4; ++mf) a[kit][mf] = load_wfrag(pbase, mf * 4 + kit);
+#pragma unroll
+    for (int kit = 0; kit < 4; ++kit) {
+        const int k0 = kit * 32 + l4 * 8;
+        bf16x8 b[2];
+#pragma unroll
+        for (int ef = 0; ef < 2; ++ef) {
+            int e = we * 32 + ef * 16 + l15;
+            int byte = e * 256 + ((k0 * 2) ^ ((e & 15) << 4));
+            b[ef] = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const char*>(h_lds) + byte);
+        }
+#pragma unroll
+        for (int mf = 0; mf < 4; ++mf)
+#pragma unroll
+            for (int ef = 0; ef < 2; ++ef)
+                acc[mf][ef] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                    a[kit & 1][mf], b[ef], acc[mf][ef], 0, 0, 0);
+        if (kit + 2 < 4) {
+#pragma unroll
+            for (int mf = 0; mf < 4; ++mf)
+                a[kit & 1][mf] = load_wfrag(pbase, mf * 4 + kit + 2);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+template <int O, typename TD>
+__device__ __forceinline__ void du_store_cell(TD* __restrict__ dst, const float (&s)[O]) {
+    constexpr int OP = opad_of(O);
+    if constexpr (O == 1) {
+        dst[0] = (TD)s[0];
+    } else if constexpr (sizeof(TD) == 4) {
+#pragma unroll
+        for (int q = 0; q < OP / 4; ++q) {
+            f32x4 v;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = (q * 4 + j < O) ? s[q * 4 + j] : 0.f;
+            *reinterpret_cast<f32x4*>(dst + q * 4) = v;
+        }
+    } else {
+        typename OVec<OP>::type v;
+#pragma unroll
+        for (int j = 0; j < OP; ++j) v[j] = (j < O) ? (__bf16)s[j] : (__bf16)0.f;
+        *reinterpret_cast<typename OVec<OP>::type*>(dst) = v;
+    }
+}
+
+template <int O, typename TD>
 __global__ void __launch_bounds__(NT, 4)   // cap VGPR<=128: 2 blocks/CU
 pairconv_bwd_du_kernel(const __bf16* __restrict__ H,   // (E,128)
                        const __bf16* __restrict__ P,   // packed W as forward
                        const float* __restrict__ bias, // (mo*miF,)
                        const __bf16* __restrict__ Gt,  // (mo, E, OP)
-                       float* __restrict__ dU,         // (miF, E, OP) f32, pads written 0
+                       TD* __restrict__ dU,            // (miF, E, OP), pads written 0
                        int E, int mo, int miF, int nmemb, int coh) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    __bf16* h_lds = reinterpret_cast<__bf16*>(smem);                   // [64][128] swizzled 16K
-    __bf16* r_lds = reinterpret_cast<__bf16*>(smem + 16384);           // [256n][64e] 32K
-    // g and du_acc stay [row][o][e] in LDS, e on the lanes: the contraction
-    // reads scalars that load straight into the high half of a register, so
-    // it converts nothing. Reading g as [m][e][OP] vectors there was tried
-    // two ways and lost (unpacking the vector, +10 % at O=7; per-element
-    // dot2 against (R, 0), +9 % at O=5; profiles/opad_layout.md). The g
-    // vectors are split by the commit, du_acc is gathered by the final write.
     constexpr int OP = opad_of(O);
     typedef typename OVec<OP>::type ovec;
-    __bf16* g_lds = reinterpret_cast<__bf16*>(smem + 49152);           // [8][O][64]
-    float* du_acc = reinterpret_cast<float*>(smem + 49152 + ((8 * O * 64 * 2 + 15) & ~15)); // [32][O][64]
-    float* bias_lds = reinterpret_cast<float*>(
-        smem + 49152 + ((8 * O * 64 * 2 + 15) & ~15) + 32 * O * 64 * 4);  // [256]
+    constexpr int GT = 8 * 64 * OP;                                    // g tile, elements
+    __bf16* h_lds = reinterpret_cast<__bf16*>(smem);                   // [64][128] swizzled 16K
+    constexpr int RB = 64 * DU_RP * 2;                                 // R bounce, bytes
+    __bf16* r_lds = reinterpret_cast<__bf16*>(smem + 16384);           // [64e][DU_RP] 33K
+    __bf16* g_lds = reinterpret_cast<__bf16*>(smem + 16384 + RB);      // [2][8][64][OP]
+    float* bias_lds = reinterpret_cast<float*>(smem + 16384 + RB + 2 * GT * 2);  // [2][256]
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
-    const int wid = tid >> 6;
+    // the wave index as a scalar: the W-fragment addresses are then a scalar
+    // base plus one lane offset, not 64-bit vector pointers that the
+    // accumulators would push into scratch
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15;
     const int l4 = lane >> 4;
     const int wm = wid >> 1;
@@ -446,18 +558,18 @@ pairconv_bwd_du_kernel(const __bf16* __restrict__ H,   // (E,128)
     const int uc0 = cb * 32;          // urow chunk
 
     stage_h_tile(h_lds, H, e0, E, tid);
-    for (int i = tid; i < 32 * O * 64; i += NT) du_acc[i] = 0.f;
+
+    float du[4][O];                   // cells (e = lane, c = 4 wid + k)
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int o = 0; o < O; ++o) du[k][o] = 0.f;
 
     // T14 register staging: the next mo-block's g tile + bias chunk load
     // while the current block's MFMA + contraction run (the g tile is one
     // (m, e) vector per thread; at O=1, 8 edges of one m for 64 threads).
     // The g load is a bare predicated load into a register zeroed once (a
     // thread's edge is in or out of range for the whole kernel).
-    // OPEN: with the contraction identical to the e-contiguous kernel's and
-    // dU bit-equal to it, du still measures 4-10 % slower than that kernel
-    // ((3,3) 16.39 vs 15.58 ms, (2,2) 11.22 vs 10.16, (1,1) 3.50 vs 3.36);
-    // this spelling, load_ovec and a coalesced output store all measure
-    // the same. The cause is not found (profiles/opad_layout.md).
     ovec g_reg(0);
     float bias_reg;
     const bool g_in = e0 + lane < E;
@@ -486,77 +598,81 @@ pairconv_bwd_du_kernel(const __bf16* __restrict__ H,   // (E,128)
     load_gb(0);
 
     const int nmo = mo / 8;
-    __syncthreads();
 
     for (int mb = 0; mb < nmo; ++mb) {
-        // commit the staged g tile as [8][O][64] + bias chunk [256]
+        // commit the staged g tile [8][64][OP] + bias chunk [256] to the
+        // buffer of this parity. Its last readers were block mb-2's, which
+        // every thread left before it passed a barrier of block mb-1.
+        __bf16* g_buf = g_lds + (mb & 1) * GT;
+        float* b_buf = bias_lds + (mb & 1) * 256;
         if constexpr (O == 1) {
-            if (tid < 64) *reinterpret_cast<bf16x8*>(g_lds + (size_t)tid * 8) = g_reg;
+            if (tid < 64) *reinterpret_cast<bf16x8*>(g_buf + (size_t)tid * 8) = g_reg;
         } else {
-#pragma unroll
-            for (int o = 0; o < O; ++o)
-                g_lds[((tid >> 6) * O + o) * 64 + lane] = g_reg[o];
+            *reinterpret_cast<ovec*>(g_buf + (size_t)tid * OP) = g_reg;
         }
-        if (tid < 256) bias_lds[tid] = bias_reg;
+        if (tid < 256) b_buf[tid] = bias_reg;
         if (mb + 1 < nmo) load_gb(mb + 1);   // issue next block's loads early
-        __syncthreads();
+        __syncthreads();   // g, bias (and h) visible; block mb-1's r_lds reads done
         // MFMA R tile (256n x 64e), A-fragments straight from the packed W
         f32x4 acc[4][2];
         const __bf16* pbase = P + ((((size_t)mb * (miF / 32) + cb) * 4 + wm) * 4) * 4 * 64 * 8
                               + (size_t)lane * 8;
-        mfma_rtile(acc, h_lds, we, l15, l4, [&](int mf, int kit) {
-            return load_wfrag(pbase, mf * 4 + kit);
-        });
-        // bounce R (+bias) to LDS [256n][64e]
+        du_rtile(acc, h_lds, pbase, we, l15, l4);
+        // bounce R (+bias) to LDS: fragment (mf, ef) holds rows
+        // r = wm*64 + mf*16 + l4*4 + reg, that is m = 2 wm + (mf >> 1),
+        // q = 4 (mf & 1) + l4, k = reg, of column e = we*32 + ef*16 + l15
+        {
+            __bf16* rb = r_lds + (size_t)(we * 32 + l15) * DU_RP + l4 * 32 + wm * 8;
+            const float* bb = b_buf + wm * 64 + l4 * 4;
 #pragma unroll
-        for (int mf = 0; mf < 4; ++mf)
+            for (int mf = 0; mf < 4; ++mf) {
+                const f32x4 b4 = *reinterpret_cast<const f32x4*>(bb + mf * 16);
 #pragma unroll
-            for (int ef = 0; ef < 2; ++ef)
+                for (int ef = 0; ef < 2; ++ef) {
+                    bf16x4 v;
 #pragma unroll
-                for (int reg = 0; reg < 4; ++reg) {
-                    int r = wm * 64 + mf * 16 + l4 * 4 + reg;
-                    int e = we * 32 + ef * 16 + l15;
-                    r_lds[(size_t)r * 64 + e] = (__bf16)(acc[mf][ef][reg] + bias_lds[r]);
+                    for (int reg = 0; reg < 4; ++reg)
+                        v[reg] = (__bf16)(acc[mf][ef][reg] + b4[reg]);
+                    *reinterpret_cast<bf16x4*>(
+                        rb + ef * 16 * DU_RP + (mf & 1) * 128 + (mf >> 1) * 4) = v;
                 }
-        __syncthreads();
-        // contraction: du_acc[c][o][e] += sum_m R[(m,c)][e] * g[m][o][e]
-        // partition (c,e) across all 512 threads: 32*64 = 2048 cells, 4 per thread
-        for (int i = tid; i < 32 * 64; i += NT) {
-            int e = i & 63, c = i >> 6;
-#pragma unroll
-            for (int o = 0; o < O; ++o) {
-                float s = du_acc[(c * O + o) * 64 + e];
-#pragma unroll
-                for (int m = 0; m < 8; ++m)
-                    s = fmaf(b2f(r_lds[(size_t)(m * 32 + c) * 64 + e]),
-                             b2f(g_lds[(m * O + o) * 64 + e]), s);
-                du_acc[(c * O + o) * 64 + e] = s;
             }
         }
         __syncthreads();
+        // contraction: du[k][o] += sum_m R[(m, c_k)][e] * g[m][e][o], m
+        // ascending, one fma per term (the order the sums always had)
+        const __bf16* gp = g_buf + (size_t)lane * OP;
+        bf16x8 rv[4];                 // R[e][q = wid][m][k]
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            rv[j] = *reinterpret_cast<const bf16x8*>(
+                r_lds + (size_t)lane * DU_RP + wid * 32 + j * 8);
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {
+            float gf[O];
+            if constexpr (O == 1) {
+                gf[0] = b2f(gp[m * 64]);
+            } else {
+                ovec gv = *reinterpret_cast<const ovec*>(gp + (size_t)m * 64 * OP);
+#pragma unroll
+                for (int o = 0; o < O; ++o) gf[o] = b2f(gv[o]);
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float r = b2f(rv[m >> 1][(m & 1) * 4 + k]);
+#pragma unroll
+                for (int o = 0; o < O; ++o) du[k][o] = fmaf(r, gf[o], du[k][o]);
+            }
+        }
     }
-    // write the du chunk as (c, e) vectors of OP floats, pads zero: 16 B
-    // units, consecutive lanes on consecutive units, so a wave's store
-    // instruction covers 1 KiB of whole lines
-    if constexpr (O == 1) {
-        for (int i = tid; i < 32 * 64; i += NT) {
-            int e = i & 63, c = i >> 6;
-            if (e0 + e < E) dU[(size_t)(uc0 + c) * E + e0 + e] = du_acc[i];
-        }
-    } else {
-        constexpr int Q = OP / 4;                 // units per (c, e)
-        for (int u = tid; u < 32 * 64 * Q; u += NT) {
-            int q = u % Q, cell = u / Q;
-            int e = cell & 63, c = cell >> 6;
-            if (e0 + e < E) {
-                f32x4 v;
+    // each cell's (c, e) vector of OP values straight from registers, pads
+    // zero; rows e >= E are not written. In bf16 a wave's store covers 64
+    // consecutive vectors.
+    if (g_in) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    v[j] = (q * 4 + j < O) ? du_acc[(c * O + q * 4 + j) * 64 + e] : 0.f;
-                *reinterpret_cast<f32x4*>(
-                    dU + ((size_t)(uc0 + c) * E + e0 + e) * OP + q * 4) = v;
-            }
-        }
+        for (int k = 0; k < 4; ++k)
+            du_store_cell<O, TD>(
+                dU + ((size_t)(uc0 + wid * 4 + k) * E + e0 + lane) * OP, du[k]);
     }
 }
 
@@ -599,23 +715,24 @@ void pairconv_bwd_dh(torch::Tensor Gt, torch::Tensor Ut, torch::Tensor Wt,
     check_launch("bwd_dh: ");
 }
 
-template <int O>
+template <int O, bool DB>
 static void launch_dw(dim3 grid, hipStream_t stream, const __bf16* Gt,
-                      const __bf16* Ut, const __bf16* Ht, float* dW,
+                      const __bf16* Ut, const __bf16* Ht, float* dW, float* db,
                       int E, int mo, int miF) {
     if constexpr (O == 1) {
         size_t lds = 16384 + (size_t)32 * 32 * 2 + (size_t)4 * 32 * 2;
-        hipLaunchKernelGGL(pairconv_bwd_dw_o1_kernel, grid,
-                           dim3(NT), lds, stream, Gt, Ut, Ht, dW, E, mo, miF);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(pairconv_bwd_dw_o1_kernel<DB>), grid,
+                           dim3(NT), lds, stream, Gt, Ut, Ht, dW, db, E, mo, miF);
     } else {
         size_t lds = 16384 + (size_t)4 * 32 * opad_of(O) * 2;   // dr | h | g[4][32][OP]
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(pairconv_bwd_dw_kernel<O>), grid,
-                           dim3(NT), lds, stream, Gt, Ut, Ht, dW, E, mo, miF);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(pairconv_bwd_dw_kernel<O, DB>), grid,
+                           dim3(NT), lds, stream, Gt, Ut, Ht, dW, db, E, mo, miF);
     }
 }
 
+// db (mo*miF,) f32 is filled too; an empty db means "not wanted"
 void pairconv_bwd_dw(torch::Tensor Gt, torch::Tensor Ut, torch::Tensor Ht,
-                     torch::Tensor dW, int64_t mo_, int64_t O_) {
+                     torch::Tensor dW, torch::Tensor db, int64_t mo_, int64_t O_) {
     int E = Ht.size(1), mo = (int)mo_, miF = Ut.size(0), O = (int)O_;
     check_opad(Gt, "G", mo, E, O, torch::kBFloat16);
     check_opad(Ut, "U", miF, E, O, torch::kBFloat16);
@@ -624,10 +741,21 @@ void pairconv_bwd_dw(torch::Tensor Gt, torch::Tensor Ut, torch::Tensor Ht,
                 dW.numel() == (int64_t)mo * miF * KDIM);
     TORCH_CHECK(mo % 4 == 0 && miF % 32 == 0);
     auto stream = at::cuda::getCurrentHIPStream();
+    const bool want_db = db.numel() > 0;
+    if (want_db)
+        TORCH_CHECK(db.is_cuda() && db.is_contiguous() && db.dtype() == torch::kFloat32 &&
+                    db.numel() == (int64_t)mo * miF, "db must be (mo*miF,) f32 or empty");
     dim3 grid((mo / 4) * (miF / 32));
-    DISPATCH_ORDER(O, kO, "O", launch_dw<kO>(
-        grid, stream, tptr<const __bf16>(Gt), tptr<const __bf16>(Ut),
-        tptr<const __bf16>(Ht), dW.data_ptr<float>(), E, mo, miF));
+    DISPATCH_ORDER(O, kO, "O", {
+        if (want_db)
+            launch_dw<kO, true>(grid, stream, tptr<const __bf16>(Gt), tptr<const __bf16>(Ut),
+                                tptr<const __bf16>(Ht), dW.data_ptr<float>(),
+                                db.data_ptr<float>(), E, mo, miF);
+        else
+            launch_dw<kO, false>(grid, stream, tptr<const __bf16>(Gt), tptr<const __bf16>(Ut),
+                                 tptr<const __bf16>(Ht), dW.data_ptr<float>(),
+                                 nullptr, E, mo, miF);
+    });
     check_launch("bwd_dw: ");
 }
 
@@ -635,7 +763,7 @@ void pairconv_bwd_du(torch::Tensor H, torch::Tensor W, torch::Tensor bias,
                      torch::Tensor Gt, torch::Tensor dU, int64_t mo_, int64_t O_) {
     int E = H.size(0), mo = (int)mo_, miF = dU.size(0), O = (int)O_;
     check_opad(Gt, "G", mo, E, O, torch::kBFloat16);
-    check_opad(dU, "dU", miF, E, O, torch::kFloat32);
+    check_opad(dU, "dU", miF, E, O, dU.scalar_type());
     TORCH_CHECK(H.is_contiguous() && W.is_contiguous() && bias.is_contiguous());
     TORCH_CHECK(H.dtype() == torch::kBFloat16 && H.size(1) == KDIM);
     TORCH_CHECK(W.numel() == (int64_t)mo * miF * KDIM, "expect packed W (P)");
@@ -646,14 +774,15 @@ void pairconv_bwd_du(torch::Tensor H, torch::Tensor W, torch::Tensor bias,
     int ncb = miF / 32;
     int coh = (ncb % 8 == 0) ? 1 : 0;
     dim3 grid(nmemb * ncb);
-    DISPATCH_ORDER(O, kO, "O", {
-        size_t lds = 49152 + (size_t)((8 * kO * 64 * 2 + 15) & ~15) +
-                     (size_t)32 * kO * 64 * 4 + 256 * 4;
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(pairconv_bwd_du_kernel<kO>),
+    DISPATCH_F32_BF16(dU, __bf16, DISPATCH_ORDER(O, kO, "O", {
+        // h | R | g [2][8][64][OP] | bias [2][256]: 68,608 B at OP = 8
+        size_t lds = 16384 + (size_t)64 * DU_RP * 2 +
+                     (size_t)2 * 8 * 64 * opad_of(kO) * 2 + 2 * 256 * 4;
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(pairconv_bwd_du_kernel<kO, T>),
                            grid, dim3(NT), lds, stream,
                            tptr<const __bf16>(H), tptr<const __bf16>(W),
                            bias.data_ptr<float>(), tptr<const __bf16>(Gt),
-                           dU.data_ptr<float>(), E, mo, miF, nmemb, coh);
-    });
+                           tptr<T>(dU), E, mo, miF, nmemb, coh);
+    }));
     check_launch("bwd_du: ");
 }

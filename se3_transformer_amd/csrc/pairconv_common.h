@@ -17,7 +17,7 @@ typedef __attribute__((ext_vector_type(2))) float f32x2;
 #define NT 512     // threads per block (8 waves) in all four kernels
 
 // Padded o width OP(O) of the edge-major tensors U (miF, E, OP) bf16,
-// G (mo, E, OP) bf16 and dU (miF, E, OP) f32: all o of one (row, edge) are
+// G (mo, E, OP) bf16 and dU (miF, E, OP) bf16 or f32: all o of one (row, edge) are
 // one aligned vector, and the pad lanes o in [O, OP) are exactly zero, so a
 // consumer contracts whole vectors. The one definition; ops/fused.py mirrors
 // it and checks pairconv_opad() at load.

@@ -3,8 +3,9 @@
 //   U[(c*F + f), e, o] = sum_i  B[e, o, i, f] * X[e, c, i]
 //
 // U is (C*F, E, OP): edge-major with o padded to OP = opad_of(O)
-// (pairconv_common.h), pad lanes written as zeros. dU has the same shape in
-// f32.
+// (pairconv_common.h), pad lanes written as zeros. dU has the same shape, in
+// bf16 as pairconv_bwd_du rounds it or in f32; the backward kernels widen it
+// into the f32 LDS tile they compute on, so both give the same bits.
 //
 // This is the `torch.einsum('eoif,eci->cfeo')` in PairwiseConv.apply_fused
 // (reference contraction se3_transformer_pytorch.py:336-338 restructured,
@@ -152,10 +153,10 @@ ubuild_gather_fwd_kernel(const float* __restrict__ B, const TX* __restrict__ Xn,
     ubuild_fwd_body<TX, OP, true>(B, Xn, rows, Ut, E, N, C, O, I, F);
 }
 
-template <typename TX>
+template <typename TX, typename TG>
 __global__ void __launch_bounds__(UB_NT)
 ubuild_bwd_dx_kernel(const float* __restrict__ B,   // (E, O, I, F)
-                     const float* __restrict__ dU,  // (C*F, E, OP) f32
+                     const TG* __restrict__ dU,     // (C*F, E, OP) f32 | bf16
                      TX* __restrict__ dX,           // (E, C, I)
                      int E, int C, int O, int I, int F) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -184,7 +185,7 @@ ubuild_bwd_dx_kernel(const float* __restrict__ B,   // (E, O, I, F)
             int c = cf / F, f = cf % F;
             if (o < O)
                 g_lds[(c * fo + f * O + o) * UB_EB + e] = (e0 + e < E)
-                    ? dU[(((size_t)(c0 + c) * F + f) * E + e0 + e) * OP + o] : 0.f;
+                    ? (float)dU[(((size_t)(c0 + c) * F + f) * E + e0 + e) * OP + o] : 0.f;
         }
         __syncthreads();
         // dX elements: (c 8) x (i I) x (e 16), e minor
@@ -212,11 +213,11 @@ ubuild_bwd_dx_kernel(const float* __restrict__ B,   // (E, O, I, F)
 // rounding of B and X.
 #define UB_DBK 22        // ceil(16 * 343 / 256)
 
-template <typename TX, bool GATHER>
+template <typename TX, typename TG, bool GATHER>
 __device__ __forceinline__ void
 ubuild_bwd_db_body(const TX* __restrict__ X,      // (E, C, I) | (N, C, I)
                    const int* __restrict__ rows,  // (E,) when GATHER
-                   const float* __restrict__ dU,  // (C*F, E, OP) f32
+                   const TG* __restrict__ dU,     // (C*F, E, OP) f32 | bf16
                    float* __restrict__ dB,        // (E, O, I, F)
                    int E, int N, int C, int O, int I, int F) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -257,7 +258,7 @@ ubuild_bwd_db_body(const TX* __restrict__ X,      // (E, C, I) | (N, C, I)
             int c = cf / F, f = cf % F;
             if (o < O)
                 g_lds[(c * fo + f * O + o) * UB_EB + e] = (e0 + e < E)
-                    ? dU[(((size_t)(c0 + c) * F + f) * E + e0 + e) * OP + o] : 0.f;
+                    ? (float)dU[(((size_t)(c0 + c) * F + f) * E + e0 + e) * OP + o] : 0.f;
         }
         for (int t = tid; t < UB_CB * I * UB_EB; t += UB_NT) {
             int r = t / UB_EB;         // c*I + i
@@ -289,21 +290,21 @@ ubuild_bwd_db_body(const TX* __restrict__ X,      // (E, C, I) | (N, C, I)
     }
 }
 
-template <typename TX>
+template <typename TX, typename TG>
 __global__ void __launch_bounds__(UB_NT)
-ubuild_bwd_db_kernel(const TX* __restrict__ X, const float* __restrict__ dU,
+ubuild_bwd_db_kernel(const TX* __restrict__ X, const TG* __restrict__ dU,
                      float* __restrict__ dB, int E, int C, int O, int I, int F) {
-    ubuild_bwd_db_body<TX, false>(X, nullptr, dU, dB, E, E, C, O, I, F);
+    ubuild_bwd_db_body<TX, TG, false>(X, nullptr, dU, dB, E, E, C, O, I, F);
 }
 
-template <typename TX>
+template <typename TX, typename TG>
 __global__ void __launch_bounds__(UB_NT)
 ubuild_gather_bwd_db_kernel(const TX* __restrict__ Xn,
                             const int* __restrict__ rows,
-                            const float* __restrict__ dU,
+                            const TG* __restrict__ dU,
                             float* __restrict__ dB,
                             int E, int N, int C, int O, int I, int F) {
-    ubuild_bwd_db_body<TX, true>(Xn, rows, dU, dB, E, N, C, O, I, F);
+    ubuild_bwd_db_body<TX, TG, true>(Xn, rows, dU, dB, E, N, C, O, I, F);
 }
 
 // dXn[rows[e], c, i] += sum_{f,o} B[e,o,i,f] * dU[(c*F+f), e, o]
@@ -314,10 +315,10 @@ ubuild_gather_bwd_db_kernel(const TX* __restrict__ Xn,
 // floats (CB is chosen by the host so a run is at least 128 B): two rows
 // per instruction, three where a 40- or 48-float run straddles, not 16. The dU tile sits [e][c][f*O+o]: lanes differ in c, F*O is odd, so
 // the compute reads are conflict-free.
-template <int CB>
+template <int CB, typename TG>
 __global__ void __launch_bounds__(UB_NT)
 ubuild_gather_bwd_dx_kernel(const float* __restrict__ B,   // (E, O, I, F)
-                            const float* __restrict__ dU,  // (C*F, E, OP) f32
+                            const TG* __restrict__ dU,     // (C*F, E, OP) f32 | bf16
                             const int* __restrict__ rows,  // (E,)
                             float* __restrict__ dXn,       // (N, C, I) f32
                             int E, int N, int C, int O, int I, int F) {
@@ -349,7 +350,7 @@ ubuild_gather_bwd_dx_kernel(const float* __restrict__ B,   // (E, O, I, F)
             int c = cf / F, f = cf % F;
             if (o < O)
                 g_lds[(e * CB + c) * fo + f * O + o] = (e0 + e < E)
-                    ? dU[(((size_t)(c0 + c) * F + f) * E + e0 + e) * OP + o] : 0.f;
+                    ? (float)dU[(((size_t)(c0 + c) * F + f) * E + e0 + e) * OP + o] : 0.f;
         }
         __syncthreads();
         // dXn elements: (e 16) x (c CB) x (i I), (c, i) minor as in memory
@@ -368,6 +369,12 @@ ubuild_gather_bwd_dx_kernel(const float* __restrict__ B,   // (E, O, I, F)
                 atomicAdd(&dXn[((size_t)row * C + c0) * I + ci], acc);
         }
     }
+}
+
+// dU arrives f32, or bf16 as pairconv_bwd_du rounds it; the staging load
+// widens to the f32 LDS tile either way.
+static bool check_du_dtype(const torch::Tensor& dU) {
+    return dU.dtype() == torch::kFloat32 || dU.dtype() == torch::kBFloat16;
 }
 
 void ubuild_fwd(torch::Tensor B, torch::Tensor X, torch::Tensor Ut,
@@ -405,8 +412,7 @@ void ubuild_fwd(torch::Tensor B, torch::Tensor X, torch::Tensor Ut,
 void ubuild_bwd_dx(torch::Tensor B, torch::Tensor dU, torch::Tensor dX,
                    int64_t O, int64_t I, int64_t F) {
     TORCH_CHECK(B.is_cuda() && B.is_contiguous() && B.dtype() == torch::kFloat32);
-    TORCH_CHECK(dU.is_contiguous() && dU.dtype() == torch::kFloat32 &&
-                dX.is_contiguous());
+    TORCH_CHECK(dU.is_contiguous() && check_du_dtype(dU) && dX.is_contiguous());
     int E = B.size(0);
     int C = dX.size(1);
     TORCH_CHECK(C % UB_CB == 0, "channels must be a multiple of 8");
@@ -414,23 +420,26 @@ void ubuild_bwd_dx(torch::Tensor B, torch::Tensor dU, torch::Tensor dX,
     TORCH_CHECK(O == 1 || O == 3 || O == 5 || O == 7, "unsupported O ", O);
     TORCH_CHECK(dU.numel() == (int64_t)C * F * E * opad_of((int)O),
                 "expect dU as (C*F, E, OP(O))");
+    const bool du16 = dU.dtype() == torch::kBFloat16;
     auto stream = at::cuda::getCurrentHIPStream();
     dim3 grid((E + UB_EB - 1) / UB_EB);
     size_t lds = (size_t)UB_EB * O * I * F * 4 + (size_t)UB_CB * F * O * UB_EB * 4;
+#define UB_LAUNCH_DX(TG)                                                      \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(ubuild_bwd_dx_kernel<T, TG>), grid,    \
+                       dim3(UB_NT), lds, stream, B.data_ptr<float>(),         \
+                       tptr<const TG>(dU), tptr<T>(dX),                       \
+                       E, C, (int)O, (int)I, (int)F)
     DISPATCH_F32_BF16(dX, __bf16, {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(ubuild_bwd_dx_kernel<T>), grid,
-                           dim3(UB_NT), lds, stream, B.data_ptr<float>(),
-                           dU.data_ptr<float>(), tptr<T>(dX),
-                           E, C, (int)O, (int)I, (int)F);
+        if (du16) UB_LAUNCH_DX(__bf16); else UB_LAUNCH_DX(float);
     });
+#undef UB_LAUNCH_DX
     check_launch("ubuild_bwd_dx: ");
 }
 
 void ubuild_bwd_db(torch::Tensor X, torch::Tensor dU, torch::Tensor dB,
                    int64_t O, int64_t I, int64_t F) {
     TORCH_CHECK(X.is_cuda() && X.is_contiguous() && X.dim() == 3);
-    TORCH_CHECK(dU.is_cuda() && dU.is_contiguous() &&
-                dU.dtype() == torch::kFloat32);
+    TORCH_CHECK(dU.is_cuda() && dU.is_contiguous() && check_du_dtype(dU));
     TORCH_CHECK(dB.is_cuda() && dB.is_contiguous() &&
                 dB.dtype() == torch::kFloat32);
     int E = X.size(0);
@@ -444,14 +453,18 @@ void ubuild_bwd_db(torch::Tensor X, torch::Tensor dU, torch::Tensor dB,
     if (E == 0) return;
     size_t lds = (size_t)UB_CB * UB_EB * (F * O + I) * 4;
     TORCH_CHECK(lds <= 64 * 1024, "degree pair too large for LDS staging");
+    const bool du16 = dU.dtype() == torch::kBFloat16;
     auto stream = at::cuda::getCurrentHIPStream();
     dim3 grid((E + UB_EB - 1) / UB_EB);
+#define UB_LAUNCH_DB(TG)                                                      \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(ubuild_bwd_db_kernel<T, TG>), grid,    \
+                       dim3(UB_NT), lds, stream, tptr<const T>(X),            \
+                       tptr<const TG>(dU), dB.data_ptr<float>(),              \
+                       E, C, (int)O, (int)I, (int)F)
     DISPATCH_F32_BF16(X, __bf16, {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(ubuild_bwd_db_kernel<T>), grid,
-                           dim3(UB_NT), lds, stream, tptr<const T>(X),
-                           dU.data_ptr<float>(), dB.data_ptr<float>(),
-                           E, C, (int)O, (int)I, (int)F);
+        if (du16) UB_LAUNCH_DB(__bf16); else UB_LAUNCH_DB(float);
     });
+#undef UB_LAUNCH_DB
     check_launch("ubuild_bwd_db: ");
 }
 
@@ -504,8 +517,7 @@ void ubuild_gather_fwd(torch::Tensor B, torch::Tensor Xn, torch::Tensor rows,
 void ubuild_gather_bwd_dx(torch::Tensor B, torch::Tensor dU, torch::Tensor rows,
                           torch::Tensor dXn, int64_t O, int64_t I, int64_t F) {
     TORCH_CHECK(B.is_cuda() && B.is_contiguous() && B.dtype() == torch::kFloat32);
-    TORCH_CHECK(dU.is_cuda() && dU.is_contiguous() &&
-                dU.dtype() == torch::kFloat32);
+    TORCH_CHECK(dU.is_cuda() && dU.is_contiguous() && check_du_dtype(dU));
     TORCH_CHECK(dXn.dtype() == torch::kFloat32,
                 "dXn accumulates in fp32 (zero it, cast afterwards)");
     int E = B.size(0);
@@ -528,24 +540,27 @@ void ubuild_gather_bwd_dx(torch::Tensor B, torch::Tensor dU, torch::Tensor rows,
     size_t lds = lds_of(cb);
     TORCH_CHECK(lds + UB_EB * 4 <= 64 * 1024,
                 "degree pair too large for LDS staging");
+    const bool du16 = dU.dtype() == torch::kBFloat16;
     auto stream = at::cuda::getCurrentHIPStream();
     dim3 grid((E + UB_EB - 1) / UB_EB);
-#define UB_LAUNCH_GDX(CBV)                                                    \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(ubuild_gather_bwd_dx_kernel<CBV>),     \
+#define UB_LAUNCH_GDX(CBV, TG)                                                \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(ubuild_gather_bwd_dx_kernel<CBV, TG>), \
                        grid, dim3(UB_NT), lds, stream, B.data_ptr<float>(),   \
-                       dU.data_ptr<float>(), rows.data_ptr<int>(),            \
+                       tptr<const TG>(dU), rows.data_ptr<int>(),              \
                        dXn.data_ptr<float>(), E, N, C, (int)O, (int)I, (int)F)
-    if (cb == 32) UB_LAUNCH_GDX(32);
-    else if (cb == 16) UB_LAUNCH_GDX(16);
-    else UB_LAUNCH_GDX(8);
+#define UB_LAUNCH_GDX_CB(TG)                                                  \
+    if (cb == 32) UB_LAUNCH_GDX(32, TG);                                      \
+    else if (cb == 16) UB_LAUNCH_GDX(16, TG);                                 \
+    else UB_LAUNCH_GDX(8, TG)
+    if (du16) { UB_LAUNCH_GDX_CB(__bf16); } else { UB_LAUNCH_GDX_CB(float); }
+#undef UB_LAUNCH_GDX_CB
 #undef UB_LAUNCH_GDX
     check_launch("ubuild_gather_bwd_dx: ");
 }
 
 void ubuild_gather_bwd_db(torch::Tensor Xn, torch::Tensor rows, torch::Tensor dU,
                           torch::Tensor dB, int64_t O, int64_t I, int64_t F) {
-    TORCH_CHECK(dU.is_cuda() && dU.is_contiguous() &&
-                dU.dtype() == torch::kFloat32);
+    TORCH_CHECK(dU.is_cuda() && dU.is_contiguous() && check_du_dtype(dU));
     TORCH_CHECK(dB.is_cuda() && dB.is_contiguous() &&
                 dB.dtype() == torch::kFloat32);
     TORCH_CHECK(dB.dim() == 4, "expect dB as (E, O, I, F)");
@@ -560,13 +575,17 @@ void ubuild_gather_bwd_db(torch::Tensor Xn, torch::Tensor rows, torch::Tensor dU
     if (E == 0) return;
     size_t lds = (size_t)UB_CB * UB_EB * (F * O + I) * 4;
     TORCH_CHECK(lds <= 64 * 1024, "degree pair too large for LDS staging");
+    const bool du16 = dU.dtype() == torch::kBFloat16;
     auto stream = at::cuda::getCurrentHIPStream();
     dim3 grid((E + UB_EB - 1) / UB_EB);
+#define UB_LAUNCH_GDB(TG)                                                     \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(ubuild_gather_bwd_db_kernel<T, TG>),   \
+                       grid, dim3(UB_NT), lds, stream, tptr<const T>(Xn),     \
+                       rows.data_ptr<int>(), tptr<const TG>(dU),              \
+                       dB.data_ptr<float>(), E, N, C, (int)O, (int)I, (int)F)
     DISPATCH_F32_BF16(Xn, __bf16, {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(ubuild_gather_bwd_db_kernel<T>), grid,
-                           dim3(UB_NT), lds, stream, tptr<const T>(Xn),
-                           rows.data_ptr<int>(), dU.data_ptr<float>(),
-                           dB.data_ptr<float>(), E, N, C, (int)O, (int)I, (int)F);
+        if (du16) UB_LAUNCH_GDB(__bf16); else UB_LAUNCH_GDB(float);
     });
+#undef UB_LAUNCH_GDB
     check_launch("ubuild_gather_bwd_db: ");
 }

@@ -274,10 +274,11 @@ class _FusedPairConvOpad(torch.autograd.Function):
 
     H (E,128) bf16 | W (mo*miF,128) fp32/bf16 param | bias (mo*miF,) fp32
     U (miF,E,OP) bf16, pad lanes o in [O, OP) exactly zero | returns
-    (E, mo, O) fp32. The gradient of U comes back (miF,E,OP) fp32 with zero
-    pads. The kernels contract whole padded vectors and the two library
-    GEMMs (bias term, db) read U and G as (rows, E*OP) matrices: both rely
-    on the zero pads.
+    (E, mo, O) fp32. The gradient of U comes back (miF,E,OP) with zero
+    pads, in bf16 (the du kernel rounds its fp32 sums once, as autograd's
+    cast to U's dtype did) or in fp32 with SE3_TORCH_BWD. The kernels
+    contract whole padded vectors and the bias term's library GEMM reads U
+    as a (miF, E*OP) matrix: both rely on the zero pads.
     """
 
     @staticmethod
@@ -371,20 +372,21 @@ def _pairconv_backward(ctx, H16, wsave, b16, U16, grad_out, needs):
             dH = torch.zeros(E, K, dtype=torch.float32, device=H16.device)
             ext.pairconv_bwd_dh(G, U16, P1, dH, mo, O)
         P1 = None
-        if need_W:
+        if need_W or need_b:
+            # db[(m,c)] = sum_e dR[e,(m,c)]: the dw kernel sums the fp32 dR
+            # entries it builds anyway (an empty db: not wanted)
             Ht = H16.t().contiguous()              # (128, E)
             dW = torch.empty(mo * miF, K, dtype=torch.float32,
                              device=H16.device)
-            ext.pairconv_bwd_dw(G, U16, Ht, dW, mo, O)
-            dW = dW.to(ctx.w_dtype)
+            db = torch.empty(mo * miF if need_b else 0, dtype=torch.float32,
+                             device=H16.device)
+            ext.pairconv_bwd_dw(G, U16, Ht, dW, db, mo, O)
+            dW = dW.to(ctx.w_dtype) if need_W else None
+            db = db.to(ctx.b_dtype) if need_b else None
             del Ht
-        if need_b:
-            # db[(m,c)] = sum_{e,o} g[m,e,o] u[c,e,o] — one GEMM, both
-            # operands are free (mo,E*OP)/(miF,E*OP) views
-            db = (G.view(mo, E * OP) @ U16.view(miF, E * OP).t()) \
-                .reshape(mo * miF).to(ctx.b_dtype)
         if need_u:
-            dU = torch.empty(miF, E, OP, dtype=torch.float32,
+            # bf16 as U: the kernel rounds its fp32 sums once
+            dU = torch.empty(miF, E, OP, dtype=torch.bfloat16,
                              device=H16.device)
             ext.pairconv_bwd_du(H16, Pu, b16.float().reshape(-1),
                                 G, dU, mo, O)
@@ -625,7 +627,7 @@ class _UBuildFn(torch.autograd.Function):
         ext = _load_ext()
         B = ctx.saved_tensors[0]
         dtype, (E, C, I_), O, I, F = ctx.meta
-        dU = dU.contiguous().float()                   # (C*F, E, OP)
+        dU = dU.contiguous()       # (C*F, E, OP), bf16 as U: read as is
         dX = dB = None
         if ctx.needs_input_grad[0]:
             dX = torch.empty(E, C, I, dtype=dtype, device=B.device)
@@ -693,9 +695,10 @@ class _PairConvNodesFn(torch.autograd.Function):
         dXn = dB = None
         if dU is not None:
             # between _FusedPairConvOpad and _UBuildFn autograd casts dU to
-            # the dtype of U, bf16: the same rounding here keeps dXn and dB
+            # the dtype of U, bf16. The du kernel has rounded it already; the
+            # fp32 dU of SE3_TORCH_BWD is rounded here, so dXn and dB stay
             # those of the unfused path
-            dU = dU.to(torch.bfloat16).float()
+            dU = dU.to(torch.bfloat16)
         if need_X:
             # zeroed here, inside whatever graph captures the backward
             dXn = torch.zeros(Xc.shape, dtype=torch.float32, device=Xc.device)
