@@ -49,6 +49,24 @@ __device__ __forceinline__ int rt_swz(int e, int k) {
     return e * 256 + ((((k >> 3) ^ (e & 15)) << 4)) + (k & 7) * 2;  // byte
 }
 
+// LayerNorm statistics of one 128-feature row held by a wave, two features
+// per lane: the mean, then the variance as the mean of (y - mean)^2. The
+// one-pass form sum(y^2)/128 - mean^2 cancels in fp32 once the row's common
+// offset is large against its scatter (a bias LayerNorm itself is blind
+// to), and can go negative.
+__device__ __forceinline__ void rt_row_stats(const float (&y)[2], float eps,
+                                             float& mean, float& rs) {
+    float s = y[0] + y[1];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    mean = s * (1.f / RT_K);
+    const float c0 = y[0] - mean, c1 = y[1] - mean;
+    float q = c0 * c0 + c1 * c1;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) q += __shfl_xor(q, off);
+    rs = rsqrtf(q * (1.f / RT_K) + eps);
+}
+
 // ---------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------
@@ -95,15 +113,8 @@ radial_trunk_fwd_kernel(const __bf16* __restrict__ X,    // (E, D)
                 acc = fmaf(xe_lds[e * D + d], rt_b2f(W0[(size_t)k * D + d]), acc);
             y[h] = acc;
         }
-        float s = y[0] + y[1], q = y[0] * y[0] + y[1] * y[1];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            s += __shfl_xor(s, off);
-            q += __shfl_xor(q, off);
-        }
-        const float mean = s * (1.f / RT_K);
-        const float var = q * (1.f / RT_K) - mean * mean;
-        const float rs = rsqrtf(var + eps);
+        float mean, rs;
+        rt_row_stats(y, eps, mean, rs);
         if (lane == 0 && e0 + e < E) rs01[e0 + e] = rs;
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -154,15 +165,8 @@ radial_trunk_fwd_kernel(const __bf16* __restrict__ X,    // (E, D)
     for (int le = 0; le < 8; ++le) {
         const int e = w * 8 + le;
         float y[2] = {y3_lds[e * RT_PITCH + lane], y3_lds[e * RT_PITCH + lane + 64]};
-        float s = y[0] + y[1], q = y[0] * y[0] + y[1] * y[1];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            s += __shfl_xor(s, off);
-            q += __shfl_xor(q, off);
-        }
-        const float mean = s * (1.f / RT_K);
-        const float var = q * (1.f / RT_K) - mean * mean;
-        const float rs = rsqrtf(var + eps);
+        float mean, rs;
+        rt_row_stats(y, eps, mean, rs);
         if (e0 + e >= E) continue;
         if (lane == 0) rs01[E + e0 + e] = rs;
 #pragma unroll

@@ -180,9 +180,9 @@ class RadialFunc(nn.Module):
         HIP kernel each way (csrc/radial.hip); eager fallback otherwise."""
         from ..ops import fused as _fused
         in_dim = x.shape[-1]
-        if _fused.radial_ok(x, self.mid_dim):
-            n0, ln1 = self.net[0], self.net[1]
-            n3, ln4 = self.net[3], self.net[4]
+        n0, ln1 = self.net[0], self.net[1]
+        n3, ln4 = self.net[3], self.net[4]
+        if _fused.radial_ok(x, self.mid_dim, ln1.eps, ln4.eps):
             lead = x.shape[:-1]
             h = _fused.radial_trunk(x.reshape(-1, in_dim),
                                     n0.weight, n0.bias, ln1.weight, ln1.bias,

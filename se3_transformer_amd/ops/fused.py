@@ -174,8 +174,9 @@ def radial_trunk_ok(in_dim: int, mid_dim: int) -> bool:
     return mid_dim == 128 and in_dim in RADIAL_TRUNK_DIMS and ext_available()
 
 
-def radial_ok(x, mid_dim: int) -> bool:
-    return (x.is_cuda and not switch_on('SE3_EAGER_RADIAL')
+def radial_ok(x, mid_dim: int, eps0: float = 1e-5, eps3: float = 1e-5) -> bool:
+    """The kernel has one eps for both LayerNorms (net.1 and net.4)."""
+    return (x.is_cuda and eps0 == eps3 and not switch_on('SE3_EAGER_RADIAL')
             and radial_trunk_ok(x.shape[-1], mid_dim))
 
 
@@ -795,8 +796,12 @@ class _RadialTrunkFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w0, b0, g0, be0, w3, b3, g3, be3, eps):
-        ext = _load_ext()
         E, D = x.shape
+        ctx.x_dtype = x.dtype
+        if E == 0:      # nothing to launch: a grid of 0 blocks is an error
+            ctx.shapes = [t.shape for t in (x, w0, b0, g0, be0, w3, b3, g3, be3)]
+            return torch.empty(0, 128, dtype=torch.bfloat16, device=x.device)
+        ext = _load_ext()
         x16 = x.contiguous().to(torch.bfloat16)
         w0_16 = w0.detach().contiguous().to(torch.bfloat16)
         w3_16 = w3.detach().contiguous().to(torch.bfloat16)
@@ -811,11 +816,15 @@ class _RadialTrunkFn(torch.autograd.Function):
         ext.radial_trunk_fwd(x16, w0_16, p0, w3_16, p3, H, yh0, yh3, rs, eps)
         ctx.save_for_backward(x16, w0_16, p0, w3_16, p3, yh0, yh3, rs)
         ctx.eps = eps
-        ctx.x_dtype = x.dtype
         return H
 
     @staticmethod
     def backward(ctx, dH):
+        if dH.shape[0] == 0:
+            grads = [torch.zeros(s, dtype=torch.float32, device=dH.device)
+                     for s in ctx.shapes]
+            return ((grads[0].to(ctx.x_dtype) if ctx.needs_input_grad[0]
+                     else None), *grads[1:], None)
         ext = _load_ext()
         x16, w0_16, p0, w3_16, p3, yh0, yh3, rs = ctx.saved_tensors
         E, D = x16.shape

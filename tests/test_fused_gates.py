@@ -58,6 +58,48 @@ def test_the_loader_is_touched_last(monkeypatch):
     assert not fused.norm_shapes_ok(fused.NORM_GATED_MAX_C + 1, 3, True)
 
 
+def test_radial_gate_wants_one_eps_for_both_layernorms(monkeypatch):
+    """The kernel takes one eps: a trunk whose two LayerNorms differ in it
+    stays eager, decided before the extension is looked at."""
+    install_ext(monkeypatch, stub_ext())
+    x = _t(512, 3)
+    assert fused.radial_ok(x, 128) and fused.radial_ok(x, 128, 1e-6, 1e-6)
+    monkeypatch.setattr(fused, '_load_ext',
+                        lambda: pytest.fail('the extension loader was touched'))
+    assert not fused.radial_ok(x, 128, 1e-5, 1e-6)
+
+    from se3_transformer_amd.models.core import RadialFunc
+    seen = []
+    monkeypatch.setattr(fused, 'radial_ok',
+                        lambda x, mid, *eps: seen.append(eps) or False)
+    rp = RadialFunc(1, 1, 1, edge_dim=2)
+    rp.net[4].eps = 1e-3
+    rp.hidden(torch.zeros(4, 3))
+    assert seen == [(1e-5, 1e-3)]
+
+
+@pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize('need_x', [False, True])
+def test_radial_trunk_of_no_edges_never_reaches_the_extension(monkeypatch,
+                                                              dtype, need_x):
+    monkeypatch.setattr(fused, '_load_ext',
+                        lambda: pytest.fail('the extension loader was touched'))
+    from se3_transformer_amd.models.core import RadialFunc
+    rp = RadialFunc(1, 1, 1, edge_dim=2)
+    params = [p for n, p in rp.named_parameters() if not n.startswith('net.6')]
+    x = torch.zeros(0, 3, dtype=dtype, requires_grad=need_x)
+    H = fused.radial_trunk(x, *params)
+    assert H.shape == (0, 128) and H.dtype == torch.bfloat16
+    H.backward(torch.zeros(0, 128, dtype=torch.bfloat16))
+    for p in params:
+        assert p.grad is not None and p.grad.shape == p.shape
+        assert p.grad.dtype == torch.float32 and not p.grad.any()
+    if need_x:
+        assert x.grad.shape == (0, 3) and x.grad.dtype == dtype
+    else:
+        assert x.grad is None
+
+
 def test_readme_lists_exactly_the_switch_table():
     with open(README) as f:
         cells = [line.split('|')[1] for line in f if line.startswith('| `')]
