@@ -24,35 +24,58 @@
 
 // ---------------------------------------------------------------------------
 // B1: dH[e,k] = sum_n dR[e,n] W[n,k]
-// block: 64 e x 128 k, loops (mo-block 8) x (urow-chunk 32) over all n.
-// Wt is W transposed: (128, mo*miF) bf16, so the MFMA B-operand
-// (8 consecutive n at fixed k) is a contiguous 16B load.
+// block: 64 e x 128 k, loops (urow-chunk 32) x (mo-block 8) over its n; a
+// tile is 64 e x 256 n x 128 k. The W fragments come packed (P1) so the MFMA
+// operand of a lane (8 consecutive n at fixed k) is one 16 B load.
+//
+// dR build: a thread owns e = lane and the run of 8 urows c = 8 (wid & 3)..
+// of the chunk, and keeps those eight u[c][e] vectors in registers for all
+// tiles of the chunk: u never goes through LDS. Per tile it contracts them
+// with the g vectors of its four m = (wid >> 2) + 2 it (v_dot2_f32_bf16) and
+// writes one swizzled 16 B run of the [64 e][256 n] bf16 dR tile per m. The
+// next chunk's u is loaded into the same registers right after the last
+// build of a chunk, ahead of that tile's W loads: it is in flight together
+// with them and under the MFMA phase, and costs no second set of registers.
+// O=1 has no o-vector and keeps its u chunk in LDS ([row][E] tensors
+// scattered into 8-wide slots), 8 KiB more.
+//
+// MFMA phase: wave wid owns all 64 e x the 16 k of fragment wid of P1's
+// [wk2][kf4], so every W fragment is fetched once per block (32 KiB of the
+// 64 KiB tile per SIMD pair, not four times over) and meets four dR
+// fragments from LDS. The W fragments sit in an explicit ring four n-steps
+// deep (16 VGPRs); eight deep spilled at O >= 5. Every (e, k) sum runs over
+// the n-steps of a tile and over the tiles in the one order it always had,
+// so with nsplit = 1 dH is bit for bit what the (we4, wk2) mapping gave.
+// LDS: dR 32 KiB + g 8 KiB at OP = 8: two blocks per CU by LDS and by the
+// 128-VGPR cap (profiles/dh_wshare.md).
 // ---------------------------------------------------------------------------
+#define DH_RD 4   // W ring depth, n-steps
+
 template <int O>
-__global__ void __launch_bounds__(NT)
+__global__ void __launch_bounds__(NT, 4)   // cap VGPR<=128: 2 blocks/CU
 pairconv_bwd_dh_kernel(const __bf16* __restrict__ Gt,  // (mo, E, OP) bf16
                        const __bf16* __restrict__ Ut,  // (miF, E, OP) bf16
                        const __bf16* __restrict__ P1,  // packed W: [mo/8][miF/32][wk2][kf4][ns8][lane64][8]
                        float* __restrict__ dH,         // (E, 128) f32 (zeroed)
                        int E, int mo, int miF, int nsplit, int nmemb) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    // u/g tiles are [row][e][o PADDED to LP], as in memory: the dR build
-    // reads ONE vector per (row, e) and contracts with v_dot2_f32_bf16 — no
-    // scalar LDS reads, no bf16->f32 conversion ops. O=1 scatters its
-    // [row][E] tensors into 8-wide slots.
+    // the g tile (and at O=1 the u chunk) is [row][e][o PADDED to LP], as in
+    // memory: the dR build reads ONE vector per (row, e) and contracts with
+    // v_dot2_f32_bf16 — no scalar LDS reads, no bf16->f32 conversion ops.
     constexpr int LP = (O == 1) ? 8 : opad_of(O);
+    constexpr bool UREG = O != 1;     // u of a chunk in registers
     typedef typename OVec<LP>::type ovec;
     __bf16* dr_lds = reinterpret_cast<__bf16*>(smem);                 // [64e][256n] 32 KiB
-    __bf16* u_lds = reinterpret_cast<__bf16*>(smem + 32768);          // [32][64][LP]
-    __bf16* g_lds = u_lds + 32 * 64 * LP;                             // [8][64][LP]
+    __bf16* g_lds = reinterpret_cast<__bf16*>(smem + 32768);          // [8][64][LP]
+    __bf16* u_lds = g_lds + 8 * 64 * LP;                              // [32][64][8], O=1 only
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
-    const int wid = tid >> 6;
+    // the wave index as a scalar: the W-fragment addresses are a scalar base
+    // plus one lane offset
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15;
     const int l4 = lane >> 4;
-    const int we = wid >> 1;          // 0..3: e-group of 16
-    const int wk = wid & 1;           // 0..1: k-group of 64
     // panel mapping: the grid is cut into panels of PS split-slices x PE
     // e-blocks, numbered e-block fastest, so the blocks in flight together
     // re-read the packed-W of few split-slices and the u/g tiles of few
@@ -66,21 +89,20 @@ pairconv_bwd_dh_kernel(const __bf16* __restrict__ Gt,  // (mo, E, OP) bf16
     if (eb >= nmemb || sp >= nsplit) return;
     const int e0 = eb * 64;
 
-    f32x4 acc[4];                      // 16 e x 64 k per wave
+    f32x4 acc[4];                      // 64 e (4 fragments) x 16 k per wave
 #pragma unroll
-    for (int i = 0; i < 4; ++i) acc[i] = {0.f, 0.f, 0.f, 0.f};
+    for (int ef = 0; ef < 4; ++ef) acc[ef] = {0.f, 0.f, 0.f, 0.f};
 
     const int nmo = mo / 8, nuc = miF / 32;
     const int mb_lo = (nmo / nsplit) * sp;
     const int mb_hi = mb_lo + nmo / nsplit;
 
-    // T14 register staging: next g tile (every mb) and a slice of the next
-    // u chunk (every cb) load under the dR + MFMA phases. A staging unit is
-    // one (row, e) vector; at O=1 it is 8 edges of one row.
+    // T14 register staging: the next g tile (every mb) loads under the dR +
+    // MFMA phases. A staging unit is one (row, e) vector; at O=1 it is 8
+    // edges of one row.
     constexpr int GTOT = (O == 1) ? (8 * 64) / 8 : 8 * 64;      // g tile units (<= NT)
-    constexpr int UTOTd = (O == 1) ? (32 * 64) / 8 : 32 * 64;   // u chunk units
-    constexpr int UUD = 16 / LP;               // staged u units per thread (8 VGPRs)
-    ovec g_reg, u_reg[UUD];
+    constexpr int UTOT1 = (32 * 64) / 8;                        // u chunk units at O=1 (<= NT)
+    ovec g_reg;
     auto ld_unit = [&](const __bf16* __restrict__ T, int row0, int i) -> ovec {
         if constexpr (O == 1)
             return load_edges8(T + (size_t)(row0 + (i >> 3)) * E, e0 + (i & 7) * 8, E);
@@ -94,31 +116,42 @@ pairconv_bwd_dh_kernel(const __bf16* __restrict__ Gt,  // (mo, E, OP) bf16
     auto load_g = [&](int mb) {
         if (tid < GTOT) g_reg = ld_unit(Gt, mb * 8, tid);
     };
-    auto load_u = [&](int cb) {
+    // u: the thread's own eight vectors (e = lane, c = crun + j), bare
+    // predicated loads into registers zeroed once (a thread's edge is in or
+    // out of range for the whole kernel). At O=1 one staged unit of the
+    // chunk, committed to u_lds at the top of the chunk.
+    constexpr int NU = UREG ? 8 : 1;
+    ovec u[NU];
 #pragma unroll
-        for (int t = 0; t < UUD; ++t) {
-            int i = tid + t * NT;
-            if (i < UTOTd) u_reg[t] = ld_unit(Ut, cb * 32, i);
+    for (int j = 0; j < NU; ++j) u[j] = ovec(0);
+    const int crun = (wid & 3) * 8;
+    const bool e_in = e0 + lane < E;
+    auto load_u = [&](int cb) {
+        if constexpr (UREG) {
+            if (e_in) {
+                const __bf16* up = Ut + ((size_t)(cb * 32 + crun) * E + e0 + lane) * LP;
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+                    u[j] = *reinterpret_cast<const ovec*>(up + (size_t)j * E * LP);
+            }
+        } else {
+            if (tid < UTOT1) u[0] = ld_unit(Ut, cb * 32, tid);
         }
     };
     load_u(0);
     load_g(mb_lo);
     if constexpr (O == 1) {   // pad lanes of the scatter slots, cleared once
-        for (int i = tid; i < (32 + 8) * 64; i += NT)
-            *reinterpret_cast<bf16x8*>(u_lds + (size_t)i * 8) = bf16x8(0);
+        for (int i = tid; i < (8 + 32) * 64; i += NT)
+            *reinterpret_cast<bf16x8*>(g_lds + (size_t)i * 8) = bf16x8(0);
     }
 
     for (int cb = 0; cb < nuc; ++cb) {
-        // commit the staged u chunk [urow][e][LP]
-        __syncthreads();
-#pragma unroll
-        for (int t = 0; t < UUD; ++t) {
-            int i = tid + t * NT;
-            if (i < UTOTd) st_unit(u_lds, i, u_reg[t]);
+        if constexpr (!UREG) {
+            // commit the staged u chunk [urow][e][8]
+            __syncthreads();
+            if (tid < UTOT1) st_unit(u_lds, tid, u[0]);
+            if (cb + 1 < nuc) load_u(cb + 1);
         }
-        for (int i = tid + UUD * NT; i < UTOTd; i += NT)     // unstaged tail
-            st_unit(u_lds, i, ld_unit(Ut, cb * 32, i));
-        if (cb + 1 < nuc) load_u(cb + 1);
         for (int mb = mb_lo; mb < mb_hi; ++mb) {
             // commit the staged g tile [m][e][LP]
             if (tid < GTOT) st_unit(g_lds, tid, g_reg);
@@ -127,58 +160,69 @@ pairconv_bwd_dh_kernel(const __bf16* __restrict__ Gt,  // (mo, E, OP) bf16
             // cooperative dR tile [64e][256n]: thread owns (e, run of 8 n);
             // per n: one g vector (shared over the run) dot one u vector
             // via LP/2 v_dot2_f32_bf16; one swizzled b128 write per run.
-            for (int i = tid; i < (64 * 256) / 8; i += NT) {
-                int e = i & 63, n8 = i >> 6;
-                int m = n8 >> 2;                      // (n8*8)>>5
+#pragma unroll
+            for (int it = 0; it < 4; ++it) {
+                const int e = lane, n8 = wid + 8 * it;
+                const int m = n8 >> 2;
                 ovec g8 = *reinterpret_cast<const ovec*>(
                     g_lds + ((size_t)m * 64 + e) * LP);
                 __bf16 v0[8];
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    int c = (n8 * 8 + j) & 31;
-                    ovec u8 = *reinterpret_cast<const ovec*>(
-                        u_lds + ((size_t)c * 64 + e) * LP);
+                    ovec u8;
+                    if constexpr (UREG) u8 = u[j];
+                    else u8 = *reinterpret_cast<const ovec*>(
+                        u_lds + ((size_t)(crun + j) * 64 + e) * LP);
                     v0[j] = (__bf16)dot_ovec<LP>(g8, u8);
                 }
                 *reinterpret_cast<bf16x8*>(reinterpret_cast<char*>(dr_lds)
                     + e * 512 + (((n8 ^ (e & 15)) << 4))) = *reinterpret_cast<bf16x8*>(v0);
             }
+            if constexpr (UREG) {
+                // the chunk's last build is done with u: fetch the next chunk's
+                if (mb + 1 == mb_hi && cb + 1 < nuc) load_u(cb + 1);
+            }
             __syncthreads();
-            // MFMA: dH_tile += dR(64e x 256n) @ W(256n x 128k)
-            const __bf16* pbase = P1 + ((((size_t)mb * (miF / 32) + cb) * 2 + wk) * 4) * 8 * 64 * 8
+            // MFMA: dH_tile += dR(64e x 256n) @ W(256n x 128k); this wave's
+            // fragment wid of [wk2][kf4], n-step ns
+            const __bf16* pbase = P1 + (((size_t)mb * (miF / 32) + cb) * 8 + wid) * 8 * 64 * 8
                                   + (size_t)lane * 8;
+            bf16x8 w[DH_RD];
+#pragma unroll
+            for (int s = 0; s < DH_RD; ++s)
+                w[s] = *reinterpret_cast<const bf16x8*>(pbase + (size_t)s * 64 * 8);
 #pragma unroll
             for (int ns = 0; ns < 8; ++ns) {      // 8 n-steps of 32
-                // A: dR rows e = we*16+l15, n = ns*32 + l4*8.. (mo-major inside tile)
-                int ntile = ns * 32 + l4 * 8;     // 0..255 (this is (m*32+c) packed)
-                int e_row = we * 16 + l15;
-                bf16x8 a = *reinterpret_cast<const bf16x8*>(
-                    reinterpret_cast<char*>(dr_lds) + e_row * 512
-                    + ((((ntile >> 3) ^ (e_row & 15)) << 4)));
-                // careful: dR tile n index = m*32+c, global n = (mb*8+m)*miF + cb*32 + c
+                // A: dR rows e = ef*16 + l15, n = ns*32 + l4*8.. (tile n index
+                // = m*32+c; global n = (mb*8+m)*miF + cb*32 + c). The swizzle
+                // is by l15 alone, so the four reads differ by whole rows.
+                bf16x8 a[4];
 #pragma unroll
-                for (int kf = 0; kf < 4; ++kf) {
-                    bf16x8 b = *reinterpret_cast<const bf16x8*>(
-                        pbase + ((size_t)kf * 8 + ns) * 64 * 8);
-                    acc[kf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b, a, acc[kf], 0, 0, 0);
-                }
+                for (int ef = 0; ef < 4; ++ef)
+                    a[ef] = *reinterpret_cast<const bf16x8*>(
+                        reinterpret_cast<char*>(dr_lds) + (ef * 16 + l15) * 512
+                        + (((ns * 4 + l4) ^ l15) << 4));
+#pragma unroll
+                for (int ef = 0; ef < 4; ++ef)
+                    acc[ef] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                        w[ns % DH_RD], a[ef], acc[ef], 0, 0, 0);
+                if (ns + DH_RD < 8)
+                    w[ns % DH_RD] = *reinterpret_cast<const bf16x8*>(
+                        pbase + (size_t)(ns + DH_RD) * 64 * 8);
+                __builtin_amdgcn_sched_barrier(0);
             }
         }
     }
-    // D layout from mfma(b, a): D[row=k-ish?]; operands: A-arg=b (k rows), B-arg=a (e cols)
-    // mfma(X, Y, acc): D[i][j] = sum_k X[i][k(contraction)] ... X supplies M rows.
-    // Here X = b (Wt fragment: rows k, contraction n), Y = a (dR: contraction n, cols e)
+    // mfma(X = W fragment: rows k, contraction n; Y = dR: contraction n, cols e)
     // => D rows = k, cols = e: row = l4*4+reg (k), col = l15 (e).
-    {
-        for (int kf = 0; kf < 4; ++kf) {
 #pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                int k = wk * 64 + kf * 16 + l4 * 4 + reg;
-                int e = e0 + we * 16 + l15;
-                if (e < E) atomicAdd(&dH[(size_t)e * KDIM + k], acc[kf][reg]);
-            }
+    for (int ef = 0; ef < 4; ++ef)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+            int k = wid * 16 + l4 * 4 + reg;
+            int e = e0 + ef * 16 + l15;
+            if (e < E) atomicAdd(&dH[(size_t)e * KDIM + k], acc[ef][reg]);
         }
-    }
 }
 
 // ---------------------------------------------------------------------------
@@ -706,7 +750,8 @@ void pairconv_bwd_dh(torch::Tensor Gt, torch::Tensor Ut, torch::Tensor Wt,
     dim3 grid((long)panels * PS * PE);
     DISPATCH_ORDER(O, kO, "O", {
         constexpr int LP = (kO == 1) ? 8 : opad_of(kO);
-        size_t lds = 32768 + (size_t)(32 + 8) * 64 * LP * 2;   // dr | u[32][64][LP] | g[8][64][LP]
+        // dr | g[8][64][LP], and at O=1 | u[32][64][LP]
+        size_t lds = 32768 + (size_t)(kO == 1 ? 8 + 32 : 8) * 64 * LP * 2;
         hipLaunchKernelGGL(HIP_KERNEL_NAME(pairconv_bwd_dh_kernel<kO>), grid, dim3(NT), lds, stream,
                            tptr<const __bf16>(Gt), tptr<const __bf16>(Ut),
                            tptr<const __bf16>(Wt),
