@@ -6,7 +6,10 @@
 
 using torch::Tensor;
 
-// pairconv.hip, pairconv_bwd.hip, pack_w.hip
+// pairconv.hip, pairconv_bwd.hip, pack_w.hip. Any mo, miF >= 1: mo_ of the
+// four kernels is the padded ceil8(mo) and U, G, the packs and du's bias carry
+// zero pads (pairconv_common.h); out (E, mo, O) and a 3-D dW (mo, miF, 128)
+// name the true sizes. pack_w_both takes the true mo and pads.
 int64_t pairconv_opad(int64_t O);
 void pairconv_fwd_opad(Tensor H, Tensor W, Tensor Ut, Tensor out, int64_t mo_);
 void pairconv_bwd_dh(Tensor G, Tensor U, Tensor Wt, Tensor dH, int64_t mo_, int64_t O_);

@@ -15,11 +15,15 @@
 //
 // Layouts:
 //   H   (E, 128)      bf16   radial trunk activations (k-contiguous)
-//   P   (mo*miF*128)  bf16   net.6 weight packed in MFMA A-fragment order
-//                            [mo/8][miF/32][wm4][mf4][kit4][lane64][8]
-//   U   (miF, E, OP)  bf16   basis-contracted features, edge-major with o
-//                            padded to OP(O) (pairconv_common.h), pads zero
-//   out (E, mo, O)    f32    pre-initialized with the bias term; kernel adds
+//   P   (mo_p*miF_p*128) bf16 net.6 weight packed in MFMA A-fragment order
+//                            [mo_p/8][miF_p/32][wm4][mf4][kit4][lane64][8],
+//                            rows outside the true (mo, miF) zero
+//   U   (miF_p, E, OP) bf16  basis-contracted features, edge-major with o
+//                            padded to OP(O) (pairconv_common.h), pads zero,
+//                            rows >= miF zero
+//   out (E, mo, O)    f32    pre-initialized with the bias term; kernel adds.
+//                            mo is the true width: the write-out skips the
+//                            rows mo..mo_p of the last mo-block
 //
 // Tile: block = 512 threads (8 waves) owns (64 edges) x (8*MB2 mo). The H
 // tile is staged to LDS once. The block then loops over miF in chunks of 32:
@@ -60,7 +64,8 @@ pairconv_fwd_kernel(const __bf16* __restrict__ H,
                     const __bf16* __restrict__ P,
                     const __bf16* __restrict__ Ut,   // (miF, E, OP)
                     float* __restrict__ out,
-                    int E, int mo, int miF, int nmemb, int coh) {
+                    int E, int mo /* out's, true */, int miF /* padded */,
+                    int nmemb, int coh) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // carve: H tile | u chunk | partial accumulator. The u chunk is stored
     // [urow][e][o] with o PADDED to LP, as it is in memory, so the epilogue
@@ -259,7 +264,7 @@ pairconv_fwd_kernel(const __bf16* __restrict__ H,
         int o = i % O;
         int moi = (i / O) % (BLK_MO * MB2);
         int e = i / (O * BLK_MO * MB2);
-        if (e0 + e < E) {
+        if (e0 + e < E && mo0 + moi < mo) {
             float* p = out + ((size_t)(e0 + e) * mo + mo0 + moi) * O + o;
             *p += part[((size_t)e * (BLK_MO * MB2) + moi) * O + o];
         }
@@ -282,11 +287,11 @@ pairconv_fwd_kernel(const __bf16* __restrict__ H,
 template <int O, int MB2>
 static void launch_fwd(const torch::Tensor& H, const torch::Tensor& P,
                        const torch::Tensor& Ut, torch::Tensor& out,
-                       int E, int mo, int miF) {
+                       int E, int mo, int mo_p, int miF) {
     constexpr int WP = (O == 5) ? 1 : 0;
     constexpr int UNR = (O == 3) ? 2 : 1;
     int nmemb = (E + BLK_E - 1) / BLK_E;
-    int ng = mo / (BLK_MO * MB2);
+    int ng = mo_p / (BLK_MO * MB2);
     int coh = (ng % 8 == 0) ? 1 : 0;
     size_t lds = 16384 + (size_t)UCHUNK * BLK_E * FwdLP<O>::v * 2
                  + (size_t)BLK_E * BLK_MO * MB2 * O * 4;
@@ -300,7 +305,8 @@ static void launch_fwd(const torch::Tensor& H, const torch::Tensor& P,
 
 int64_t pairconv_opad(int64_t O) { return opad_of((int)O); }
 
-// U is (miF, E, OP(O)) with zero pads; O is out's last dim.
+// U is (miF_p, E, OP(O)) with zero pads; O is out's last dim. mo_ is the
+// padded mo_p of the packed W; out has the true mo in (mo_p - 8, mo_p].
 void pairconv_fwd_opad(torch::Tensor H, torch::Tensor W, torch::Tensor Ut,
                        torch::Tensor out, int64_t mo_) {
     TORCH_CHECK(H.is_cuda() && W.is_cuda() && Ut.is_cuda() && out.is_cuda());
@@ -310,20 +316,24 @@ void pairconv_fwd_opad(torch::Tensor H, torch::Tensor W, torch::Tensor Ut,
                 out.is_contiguous());
     TORCH_CHECK(Ut.dim() == 3 && out.dim() == 3);
     int E = H.size(0);
-    int mo = (int)mo_;
+    int mo_p = (int)mo_;
+    int mo = out.size(1);
     int miF = Ut.size(0);
     int O = out.size(2);
     TORCH_CHECK(H.size(1) == KDIM, "radial hidden dim must be 128");
-    TORCH_CHECK(W.numel() == (int64_t)mo * miF * KDIM, "expect packed W");
+    TORCH_CHECK(W.numel() == (int64_t)mo_p * miF * KDIM, "expect packed W");
     TORCH_CHECK(O == 1 || O == 3 || O == 5 || O == 7, "unsupported O ", O);
     TORCH_CHECK(Ut.size(1) == E && Ut.size(2) == opad_of(O),
                 "expect U as (miF, E, OP(O))");
-    TORCH_CHECK(out.size(0) == E && out.size(1) == mo);
-    TORCH_CHECK(miF % UCHUNK == 0, "miF must be a multiple of 32");
-    TORCH_CHECK(mo % BLK_MO == 0, "mo must be a multiple of 8");
+    TORCH_CHECK(miF >= UCHUNK && miF % UCHUNK == 0,
+                "U must have ceil32(miF) rows (pad rows zero)");
+    TORCH_CHECK(mo_p >= BLK_MO && mo_p % BLK_MO == 0,
+                "mo_ must be the padded ceil8(mo)");
+    TORCH_CHECK(out.size(0) == E && mo >= 1 && ceil_mo(mo) == mo_p,
+                "expect out as (E, mo, O) with ceil8(mo) == mo_");
     DISPATCH_ORDER(O, kO, "O", {
-        if (mo % (BLK_MO * 2) == 0) launch_fwd<kO, 2>(H, W, Ut, out, E, mo, miF);
-        else launch_fwd<kO, 1>(H, W, Ut, out, E, mo, miF);
+        if (mo_p % (BLK_MO * 2) == 0) launch_fwd<kO, 2>(H, W, Ut, out, E, mo, mo_p, miF);
+        else launch_fwd<kO, 1>(H, W, Ut, out, E, mo, mo_p, miF);
     });
     check_launch("pairconv_fwd launch failed: ");
 }

@@ -5,6 +5,9 @@
 //
 // u, g and du are o-padded and edge-major (OP = opad_of(O), pads zero):
 //   U (miF, E, OP) bf16 | G (mo, E, OP) bf16 (pack_g) | dU (miF, E, OP) bf16 or f32
+// Here mo and miF are the PADDED mo_p, miF_p of pairconv_common.h: the pad
+// rows of U, G, the packed W and the bias are zero, so dh and du run on them
+// as they are. Only dw writes tensors of the true sizes, and guards them.
 // so every kernel stages whole (row, edge) vectors with plain copies. At
 // O=1 that layout is the [row][E] the kernels always read, and the O=1
 // instantiations stage as they always did.
@@ -258,9 +261,12 @@ __device__ __forceinline__ void dw_mfma_chunk(f32x4 (&acc)[2][4], const __bf16* 
     }
 }
 
-// D rows = n ((l4*4+reg within frag)), cols = k (l15)
+// D rows = n ((l4*4+reg within frag)), cols = k (l15). mo and miF are the
+// true sizes of dW (mo*miF, 128); with RAG the tile may reach past either and
+// the rows that do not exist are not stored.
+template <bool RAG>
 __device__ __forceinline__ void dw_write_tile(float* __restrict__ dW, const f32x4 (&acc)[2][4],
-                                              int mb, int cb, int miF, int wn, int wk,
+                                              int mb, int cb, int mo, int miF, int wn, int wk,
                                               int l15, int l4) {
     const size_t nbase = (size_t)(mb * 4) * miF + cb * 32;
 #pragma unroll
@@ -272,6 +278,7 @@ __device__ __forceinline__ void dw_write_tile(float* __restrict__ dW, const f32x
                 int ntile = wn * 32 + nf * 16 + l4 * 4 + reg;
                 int m = ntile >> 5, c = ntile & 31;
                 int k = wk * 64 + kf * 16 + l15;
+                if (RAG && !(mb * 4 + m < mo && cb * 32 + c < miF)) continue;
                 dW[(nbase + (size_t)m * miF + c) * KDIM + k] = acc[nf][kf][reg];
             }
 }
@@ -279,14 +286,16 @@ __device__ __forceinline__ void dw_write_tile(float* __restrict__ dW, const f32x
 // db[n] = sum_e dR[e,n] of the tile's rows n = (m, uc), m < 4: s[m] is this
 // thread's sum over its e-pair of every chunk; the 16 threads of one uc are
 // consecutive lanes. The block owns its rows, so the store is exclusive.
+template <bool RAG>
 __device__ __forceinline__ void dw_write_db(float* __restrict__ db, const float (&s)[4],
-                                            int mb, int cb, int miF, int tid) {
+                                            int mb, int cb, int mo, int miF, int tid) {
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
         float v = s[m];
 #pragma unroll
         for (int d = 8; d >= 1; d >>= 1) v += __shfl_xor(v, d, 16);
-        if ((tid & 15) == 0)
+        if ((tid & 15) == 0 &&
+            (!RAG || (mb * 4 + m < mo && cb * 32 + (tid >> 4) < miF)))
             db[(size_t)(mb * 4 + m) * miF + cb * 32 + (tid >> 4)] = v;
     }
 }
@@ -305,8 +314,10 @@ __device__ __forceinline__ void dw_write_db(float* __restrict__ db, const float 
 // 4 x 32 g vectors and the H^T tile are staged in LDS.
 // With DB the thread also sums its f32 dR entries, before their bf16
 // rounding, into db (dw_write_db); without it the kernel is what it was.
+// mo and miF are the true sizes of dW and db; G and U have the padded rows.
+// RAG: mo % 4 or miF % 32 is nonzero and the stores are guarded.
 // ---------------------------------------------------------------------------
-template <int O, bool DB>
+template <int O, bool DB, bool RAG>
 __global__ void __launch_bounds__(NT)
 pairconv_bwd_dw_kernel(const __bf16* __restrict__ Gt,  // (mo, E, OP)
                        const __bf16* __restrict__ Ut,  // (miF, E, OP)
@@ -328,8 +339,9 @@ pairconv_bwd_dw_kernel(const __bf16* __restrict__ Gt,  // (mo, E, OP)
     const int l4 = lane >> 4;
     const int wn = wid >> 1;          // 0..3: n-group of 32
     const int wk = wid & 1;           // 0..1: k-group of 64
-    const int mb = blockIdx.x / (miF / 32);     // mo-block (4 mo each)
-    const int cb = blockIdx.x % (miF / 32);     // urow chunk
+    const int ncb = RAG ? (miF + 31) / 32 : miF / 32;
+    const int mb = blockIdx.x / ncb;            // mo-block (4 mo each)
+    const int cb = blockIdx.x % ncb;            // urow chunk
     const int uc = tid >> 4;          // 0..31: this thread's urow in the chunk
     const int ue = (tid & 15) * 2;    // its e-pair in the 32-edge chunk
 
@@ -382,8 +394,8 @@ pairconv_bwd_dw_kernel(const __bf16* __restrict__ Gt,  // (mo, E, OP)
         dw_mfma_chunk(acc, dr_lds, h_lds, wn, wk, l15, l4);
     }
     __syncthreads();
-    dw_write_tile(dW, acc, mb, cb, miF, wn, wk, l15, l4);
-    if constexpr (DB) dw_write_db(db, dbs, mb, cb, miF, tid);
+    dw_write_tile<RAG>(dW, acc, mb, cb, mo, miF, wn, wk, l15, l4);
+    if constexpr (DB) dw_write_db<RAG>(db, dbs, mb, cb, mo, miF, tid);
 }
 
 // ---------------------------------------------------------------------------
@@ -393,7 +405,7 @@ pairconv_bwd_dw_kernel(const __bf16* __restrict__ Gt,  // (mo, E, OP)
 // from LDS images of the g and u rows, as e-pairs: pass j of a thread is
 // row (m = j, c = tid >> 4), the same (uc, e-pair) ownership, so db sums alike.
 // ---------------------------------------------------------------------------
-template <bool DB>
+template <bool DB, bool RAG>
 __global__ void __launch_bounds__(NT)
 pairconv_bwd_dw_o1_kernel(const __bf16* __restrict__ Gt,  // (mo, E)
                           const __bf16* __restrict__ Ut,  // (miF, E)
@@ -414,8 +426,9 @@ pairconv_bwd_dw_o1_kernel(const __bf16* __restrict__ Gt,  // (mo, E)
     const int l4 = lane >> 4;
     const int wn = wid >> 1;          // 0..3: n-group of 32
     const int wk = wid & 1;           // 0..1: k-group of 64
-    const int mb = blockIdx.x / (miF / 32);     // mo-block (4 mo each)
-    const int cb = blockIdx.x % (miF / 32);     // urow chunk
+    const int ncb = RAG ? (miF + 31) / 32 : miF / 32;
+    const int mb = blockIdx.x / ncb;            // mo-block (4 mo each)
+    const int cb = blockIdx.x % ncb;            // urow chunk
 
     f32x4 acc[2][4];                  // wave: 32 n x 64 k
 #pragma unroll
@@ -471,8 +484,8 @@ pairconv_bwd_dw_o1_kernel(const __bf16* __restrict__ Gt,  // (mo, E)
         dw_mfma_chunk(acc, dr_lds, h_lds, wn, wk, l15, l4);
     }
     __syncthreads();
-    dw_write_tile(dW, acc, mb, cb, miF, wn, wk, l15, l4);
-    if constexpr (DB) dw_write_db(db, dbs, mb, cb, miF, tid);
+    dw_write_tile<RAG>(dW, acc, mb, cb, mo, miF, wn, wk, l15, l4);
+    if constexpr (DB) dw_write_db<RAG>(db, dbs, mb, cb, mo, miF, tid);
 }
 
 // ---------------------------------------------------------------------------
@@ -760,47 +773,57 @@ void pairconv_bwd_dh(torch::Tensor Gt, torch::Tensor Ut, torch::Tensor Wt,
     check_launch("bwd_dh: ");
 }
 
-template <int O, bool DB>
+template <int O, bool DB, bool RAG>
 static void launch_dw(dim3 grid, hipStream_t stream, const __bf16* Gt,
                       const __bf16* Ut, const __bf16* Ht, float* dW, float* db,
                       int E, int mo, int miF) {
     if constexpr (O == 1) {
         size_t lds = 16384 + (size_t)32 * 32 * 2 + (size_t)4 * 32 * 2;
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(pairconv_bwd_dw_o1_kernel<DB>), grid,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(pairconv_bwd_dw_o1_kernel<DB, RAG>), grid,
                            dim3(NT), lds, stream, Gt, Ut, Ht, dW, db, E, mo, miF);
     } else {
         size_t lds = 16384 + (size_t)4 * 32 * opad_of(O) * 2;   // dr | h | g[4][32][OP]
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(pairconv_bwd_dw_kernel<O, DB>), grid,
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(pairconv_bwd_dw_kernel<O, DB, RAG>), grid,
                            dim3(NT), lds, stream, Gt, Ut, Ht, dW, db, E, mo, miF);
     }
 }
 
-// db (mo*miF,) f32 is filled too; an empty db means "not wanted"
+// db (mo*miF,) f32 is filled too; an empty db means "not wanted". G has mo_
+// rows and U miF_p rows (multiples of 4 and 32). A 2-D dW (mo_*miF_p, 128) has
+// those sizes; a 3-D dW (mo, miF, 128) names the true ones, mo <= mo_ and
+// miF <= miF_p with miF_p = ceil32(miF), and db is then (mo*miF,).
 void pairconv_bwd_dw(torch::Tensor Gt, torch::Tensor Ut, torch::Tensor Ht,
                      torch::Tensor dW, torch::Tensor db, int64_t mo_, int64_t O_) {
-    int E = Ht.size(1), mo = (int)mo_, miF = Ut.size(0), O = (int)O_;
-    check_opad(Gt, "G", mo, E, O, torch::kBFloat16);
-    check_opad(Ut, "U", miF, E, O, torch::kBFloat16);
+    int E = Ht.size(1), mo_p = (int)mo_, miF_p = Ut.size(0), O = (int)O_;
+    check_opad(Gt, "G", mo_p, E, O, torch::kBFloat16);
+    check_opad(Ut, "U", miF_p, E, O, torch::kBFloat16);
     TORCH_CHECK(Ht.is_contiguous() && Ht.dtype() == torch::kBFloat16 && Ht.size(0) == KDIM);
-    TORCH_CHECK(dW.is_contiguous() && dW.dtype() == torch::kFloat32 &&
+    TORCH_CHECK(mo_p >= 4 && mo_p % 4 == 0 && miF_p >= 32 && miF_p % 32 == 0);
+    int mo = mo_p, miF = miF_p;
+    if (dW.dim() == 3) {
+        mo = dW.size(0);
+        miF = dW.size(1);
+        TORCH_CHECK(mo >= 1 && mo <= mo_p && miF >= 1 && ceil_mif(miF) == miF_p &&
+                    dW.size(2) == KDIM, "expect dW as (mo, miF, 128) inside (mo_, ceil32(miF))");
+    }
+    TORCH_CHECK(dW.is_cuda() && dW.is_contiguous() && dW.dtype() == torch::kFloat32 &&
                 dW.numel() == (int64_t)mo * miF * KDIM);
-    TORCH_CHECK(mo % 4 == 0 && miF % 32 == 0);
     auto stream = at::cuda::getCurrentHIPStream();
     const bool want_db = db.numel() > 0;
     if (want_db)
         TORCH_CHECK(db.is_cuda() && db.is_contiguous() && db.dtype() == torch::kFloat32 &&
                     db.numel() == (int64_t)mo * miF, "db must be (mo*miF,) f32 or empty");
-    dim3 grid((mo / 4) * (miF / 32));
+    const bool rag = mo % 4 != 0 || miF % 32 != 0;
+    dim3 grid(((mo + 3) / 4) * (miF_p / 32));   // mo-blocks that hold a true row
+    float* dbp = want_db ? db.data_ptr<float>() : nullptr;
+#define DW_LAUNCH(DB, RAG)                                                          \
+    launch_dw<kO, DB, RAG>(grid, stream, tptr<const __bf16>(Gt), tptr<const __bf16>(Ut), \
+                           tptr<const __bf16>(Ht), dW.data_ptr<float>(), dbp, E, mo, miF)
     DISPATCH_ORDER(O, kO, "O", {
-        if (want_db)
-            launch_dw<kO, true>(grid, stream, tptr<const __bf16>(Gt), tptr<const __bf16>(Ut),
-                                tptr<const __bf16>(Ht), dW.data_ptr<float>(),
-                                db.data_ptr<float>(), E, mo, miF);
-        else
-            launch_dw<kO, false>(grid, stream, tptr<const __bf16>(Gt), tptr<const __bf16>(Ut),
-                                 tptr<const __bf16>(Ht), dW.data_ptr<float>(),
-                                 nullptr, E, mo, miF);
+        if (want_db) { if (rag) DW_LAUNCH(true, true); else DW_LAUNCH(true, false); }
+        else { if (rag) DW_LAUNCH(false, true); else DW_LAUNCH(false, false); }
     });
+#undef DW_LAUNCH
     check_launch("bwd_dw: ");
 }
 

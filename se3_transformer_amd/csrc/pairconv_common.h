@@ -25,6 +25,27 @@ __host__ __device__ constexpr int opad_of(int O) {
     return O == 1 ? 1 : (O <= 3 ? 4 : 8);
 }
 
+// Channel padding: the MFMA tiles are 8 mo x 32 urows, and the kernels serve
+// any mo >= 1, miF >= 1 on tensors padded to mo_p = ceil_mo(mo) and
+// miF_p = ceil_mif(miF) with exact zeros:
+//
+//   P_fwd, P_dh (packed W)  sized for (mo_p, miF_p); every row outside the
+//                           true (mo, miF) is exactly zero (pack_w_both)
+//   bias handed to du       mo_p*miF_p f32, zero outside
+//   U   (miF_p, E, OP) bf16 rows >= miF exactly zero, written by the producer
+//   G   (mo_p, E, OP) bf16  rows >= mo exactly zero, written by pack_g
+//   dU  (miF_p, E, OP)      rows >= miF are written (zeros by construction)
+//                           and ignored
+//   out (E, mo, O), dW (mo*miF, 128), db (mo*miF), dH   TRUE sizes: fwd and dw
+//                           guard their stores, nothing padded reaches autograd
+//
+// Zero W rows and zero bias give R = 0 on the pads, zero U and G rows give
+// dR = 0 there, so the pads add exact zeros to out, dH and dU and the inner
+// loops are those of the aligned case. The cost: U and dU grow by miF_p/miF
+// and the MFMA work is done on the padded tile.
+__host__ __device__ constexpr int ceil_mo(int mo) { return (mo + 7) / 8 * 8; }
+__host__ __device__ constexpr int ceil_mif(int miF) { return (miF + 31) / 32 * 32; }
+
 // The (row, edge) vector of an o-padded tensor: 16 B at OP=8, 8 B at OP=4.
 // O=1 has no vector form (its layout is the plain [row][E] the kernels
 // always used); OVec<1> only keeps the O=1 instantiations well-formed.

@@ -3,7 +3,12 @@
 //   U[(c*F + f), e, o] = sum_i  B[e, o, i, f] * X[e, c, i]
 //
 // U is (C*F, E, OP): edge-major with o padded to OP = opad_of(O)
-// (pairconv_common.h), pad lanes written as zeros. dU has the same shape, in
+// (pairconv_common.h), pad lanes written as zeros. Any C >= 1: the last
+// channel chunk is guarded. Handed a U with ceil32(C*F) rows, the forward
+// writes the rows [C*F, ceil32(C*F)) as zeros (the pad rows of the pairconv
+// layout contract), and the backward kernels read the first C*F rows of a dU
+// padded likewise. The ubuild_gather_* kernels take C % 32 == 0 only.
+// dU has the same shape, in
 // bf16 as pairconv_bwd_du rounds it or in f32; the backward kernels widen it
 // into the f32 LDS tile they compute on, so both give the same bits.
 //
@@ -63,8 +68,8 @@ __device__ __forceinline__ void
 ubuild_fwd_body(const float* __restrict__ B,   // (E, O, I, F)
                 const TX* __restrict__ X,      // (E, C, I) | (N, C, I)
                 const int* __restrict__ rows,  // (E,) when GATHER
-                __bf16* __restrict__ Ut,       // (C*F, E, OP)
-                int E, int N, int C, int O, int I, int F) {
+                __bf16* __restrict__ Ut,       // (urows, E, OP), urows >= C*F
+                int E, int N, int C, int O, int I, int F, int urows) {
     // b and x tiles are stored [.., i PADDED to 8] bf16 so each output
     // element is two 16B LDS reads + 4 v_dot2_f32_bf16 over i
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -98,8 +103,10 @@ ubuild_fwd_body(const float* __restrict__ B,   // (E, O, I, F)
         for (int t = tid; t < UB_C * UB_E * 8; t += UB_NT) {
             int c = t / (UB_E * 8), rem = t % (UB_E * 8);
             int e = rem / 8, i = rem % 8;
+            // channels past C read as zero: their rows of U, where U has
+            // them, are the zero pad rows
             x_lds[((size_t)c * UB_E + e) * 8 + i] = (__bf16)(
-                (i < I && xr >= 0)
+                (i < I && xr >= 0 && c0 + c < C)
                     ? (float)X[((size_t)xr * C + c0 + c) * I + i] : 0.f);
         }
         __syncthreads();
@@ -128,7 +135,7 @@ ubuild_fwd_body(const float* __restrict__ B,   // (E, O, I, F)
                     v[o] = (__bf16)acc;
                 }
             }
-            if (e0 + e < E) {
+            if (e0 + e < E && (c0 + c) * F + f < urows) {
                 __bf16* dst = Ut + (((size_t)(c0 + c) * F + f) * E + e0 + e) * OP;
                 if constexpr (OP == 1) dst[0] = v[0];
                 else *reinterpret_cast<typename OVec<OP>::type*>(dst) =
@@ -141,8 +148,9 @@ ubuild_fwd_body(const float* __restrict__ B,   // (E, O, I, F)
 template <typename TX, int OP>
 __global__ void __launch_bounds__(UB_NT)
 ubuild_fwd_kernel(const float* __restrict__ B, const TX* __restrict__ X,
-                  __bf16* __restrict__ Ut, int E, int C, int O, int I, int F) {
-    ubuild_fwd_body<TX, OP, false>(B, X, nullptr, Ut, E, E, C, O, I, F);
+                  __bf16* __restrict__ Ut, int E, int C, int O, int I, int F,
+                  int urows) {
+    ubuild_fwd_body<TX, OP, false>(B, X, nullptr, Ut, E, E, C, O, I, F, urows);
 }
 
 template <typename TX, int OP>
@@ -150,7 +158,7 @@ __global__ void __launch_bounds__(UB_NT)
 ubuild_gather_fwd_kernel(const float* __restrict__ B, const TX* __restrict__ Xn,
                          const int* __restrict__ rows, __bf16* __restrict__ Ut,
                          int E, int N, int C, int O, int I, int F) {
-    ubuild_fwd_body<TX, OP, true>(B, Xn, rows, Ut, E, N, C, O, I, F);
+    ubuild_fwd_body<TX, OP, true>(B, Xn, rows, Ut, E, N, C, O, I, F, C * F);
 }
 
 template <typename TX, typename TG>
@@ -184,7 +192,7 @@ ubuild_bwd_dx_kernel(const float* __restrict__ B,   // (E, O, I, F)
             int cf = r / UB_EB;        // c*F + f
             int c = cf / F, f = cf % F;
             if (o < O)
-                g_lds[(c * fo + f * O + o) * UB_EB + e] = (e0 + e < E)
+                g_lds[(c * fo + f * O + o) * UB_EB + e] = (e0 + e < E && c0 + c < C)
                     ? (float)dU[(((size_t)(c0 + c) * F + f) * E + e0 + e) * OP + o] : 0.f;
         }
         __syncthreads();
@@ -200,7 +208,7 @@ ubuild_bwd_dx_kernel(const float* __restrict__ B,   // (E, O, I, F)
             for (int f = 0; f < F; ++f)
                 for (int o = 0; o < O; ++o)
                     acc = fmaf(b[(size_t)o * I * F + f], g[(f * O + o) * UB_EB], acc);
-            if (e0 + e < E)
+            if (e0 + e < E && c0 + c < C)
                 dX[((size_t)(e0 + e) * C + c0 + c) * I + i] = (TX)acc;
         }
     }
@@ -257,13 +265,13 @@ ubuild_bwd_db_body(const TX* __restrict__ X,      // (E, C, I) | (N, C, I)
             int cf = r / UB_EB;        // c*F + f
             int c = cf / F, f = cf % F;
             if (o < O)
-                g_lds[(c * fo + f * O + o) * UB_EB + e] = (e0 + e < E)
+                g_lds[(c * fo + f * O + o) * UB_EB + e] = (e0 + e < E && c0 + c < C)
                     ? (float)dU[(((size_t)(c0 + c) * F + f) * E + e0 + e) * OP + o] : 0.f;
         }
         for (int t = tid; t < UB_CB * I * UB_EB; t += UB_NT) {
             int r = t / UB_EB;         // c*I + i
             int c = r / I, i = r % I;
-            x_lds[t] = (xr >= 0)
+            x_lds[t] = (xr >= 0 && c0 + c < C)
                 ? (float)X[((size_t)xr * C + c0 + c) * I + i] : 0.f;
         }
         __syncthreads();
@@ -377,6 +385,12 @@ static bool check_du_dtype(const torch::Tensor& dU) {
     return dU.dtype() == torch::kFloat32 || dU.dtype() == torch::kBFloat16;
 }
 
+// dU holds rows = C*F rows of E*OP, or ceil32(rows) of them (pad rows unread)
+static bool check_du_rows(const torch::Tensor& dU, int rows, int E, int O) {
+    const int64_t per = (int64_t)E * opad_of(O);
+    return dU.numel() == rows * per || dU.numel() == ceil_mif(rows) * per;
+}
+
 void ubuild_fwd(torch::Tensor B, torch::Tensor X, torch::Tensor Ut,
                 int64_t O, int64_t I, int64_t F) {
     TORCH_CHECK(B.is_cuda() && B.is_contiguous() && B.dtype() == torch::kFloat32);
@@ -386,10 +400,11 @@ void ubuild_fwd(torch::Tensor B, torch::Tensor X, torch::Tensor Ut,
     int C = X.size(1);
     TORCH_CHECK(O == 1 || O == 3 || O == 5 || O == 7, "unsupported O ", O);
     const int OP = opad_of((int)O);
-    TORCH_CHECK(Ut.dim() == 3 && Ut.size(0) == (int64_t)C * F && Ut.size(1) == E &&
-                Ut.size(2) == OP, "expect U as (C*F, E, OP(O))");
+    const int urows = Ut.dim() == 3 ? (int)Ut.size(0) : -1;
+    TORCH_CHECK(C >= 1 && (urows == C * F || urows == ceil_mif(C * (int)F)) &&
+                Ut.size(1) == E && Ut.size(2) == OP,
+                "expect U as (C*F or ceil32(C*F), E, OP(O))");
     TORCH_CHECK(B.numel() == (int64_t)E * O * I * F && X.size(0) == E && X.size(2) == I);
-    TORCH_CHECK(C % UB_C == 0, "channels must be a multiple of 32");
     TORCH_CHECK(O * I * F <= 343, "degree pair too large for LDS staging");
     TORCH_CHECK(I <= 8, "I (2*d_in+1) must be <= 8");
     auto stream = at::cuda::getCurrentHIPStream();
@@ -399,7 +414,7 @@ void ubuild_fwd(torch::Tensor B, torch::Tensor X, torch::Tensor Ut,
     hipLaunchKernelGGL(HIP_KERNEL_NAME(ubuild_fwd_kernel<T, OPV>), grid,      \
                        dim3(UB_NT), lds, stream, B.data_ptr<float>(),         \
                        tptr<const T>(X), tptr<__bf16>(Ut),                    \
-                       E, C, (int)O, (int)I, (int)F)
+                       E, C, (int)O, (int)I, (int)F, urows)
     DISPATCH_F32_BF16(X, __bf16, {
         if (OP == 8) UB_LAUNCH_FWD(8);
         else if (OP == 4) UB_LAUNCH_FWD(4);
@@ -415,11 +430,10 @@ void ubuild_bwd_dx(torch::Tensor B, torch::Tensor dU, torch::Tensor dX,
     TORCH_CHECK(dU.is_contiguous() && check_du_dtype(dU) && dX.is_contiguous());
     int E = B.size(0);
     int C = dX.size(1);
-    TORCH_CHECK(C % UB_CB == 0, "channels must be a multiple of 8");
     TORCH_CHECK(O * I * F <= 343);
     TORCH_CHECK(O == 1 || O == 3 || O == 5 || O == 7, "unsupported O ", O);
-    TORCH_CHECK(dU.numel() == (int64_t)C * F * E * opad_of((int)O),
-                "expect dU as (C*F, E, OP(O))");
+    TORCH_CHECK(C >= 1 && check_du_rows(dU, C * (int)F, E, (int)O),
+                "expect dU as (C*F or ceil32(C*F), E, OP(O))");
     const bool du16 = dU.dtype() == torch::kBFloat16;
     auto stream = at::cuda::getCurrentHIPStream();
     dim3 grid((E + UB_EB - 1) / UB_EB);
@@ -445,10 +459,8 @@ void ubuild_bwd_db(torch::Tensor X, torch::Tensor dU, torch::Tensor dB,
     int E = X.size(0);
     int C = X.size(1);
     TORCH_CHECK(O == 1 || O == 3 || O == 5 || O == 7, "unsupported O ", O);
-    TORCH_CHECK(X.size(2) == I &&
-                dU.numel() == (int64_t)C * F * E * opad_of((int)O) &&
+    TORCH_CHECK(X.size(2) == I && C >= 1 && check_du_rows(dU, C * (int)F, E, (int)O) &&
                 dB.numel() == (int64_t)E * O * I * F);
-    TORCH_CHECK(C % UB_CB == 0, "channels must be a multiple of 8");
     TORCH_CHECK(O * I * F <= 343);
     if (E == 0) return;
     size_t lds = (size_t)UB_CB * UB_EB * (F * O + I) * 4;

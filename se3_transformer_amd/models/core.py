@@ -253,7 +253,9 @@ class PairwiseConv(nn.Module):
         if _fused.pairconv_ok(xg, mo, mi * F_, O, self.rp.mid_dim):
             h = self.rp.hidden(ef)                           # (E, 128)
             # u[(mi,f), e, o] = sum_i B[e,o,i,f] x[e,mi,i], written once in
-            # the o-padded layout every pairconv kernel reads
+            # the o-padded layout every pairconv kernel reads. Any channel
+            # counts: ubuild_opad emits the rows up to ceil32(mi*F) as zeros,
+            # fused_pairconv pads an eager u likewise
             w6 = self.rp.net[6]
             if _fused.ubuild_ok(braw, mi, O, I, F_):
                 u = _fused.ubuild_opad(xg, braw.contiguous(), O, I, F_)

@@ -141,7 +141,17 @@ def knn_ok(n: int, k: int) -> bool:
 
 
 def fused_shapes_ok(mo: int, miF: int, O: int, mid_dim: int) -> bool:
-    return mid_dim == 128 and miF % 32 == 0 and mo % 8 == 0 and O in (1, 3, 5, 7)
+    """Any channel counts: the kernels run on tiles zero-padded to
+    (ceil8(mo), ceil32(miF)), see pad_dims."""
+    return mid_dim == 128 and miF >= 1 and mo >= 1 and O in (1, 3, 5, 7)
+
+
+def pad_dims(mo: int, miF: int):
+    """(mo_p, miF_p) = (ceil8(mo), ceil32(miF)): the MFMA tile of the pairconv
+    kernels (ceil_mo, ceil_mif in csrc/pairconv_common.h). Packed W, bias, U
+    and G are zero outside the true (mo, miF); out, dW and db keep the true
+    sizes."""
+    return -(-mo // 8) * 8, -(-miF // 32) * 32
 
 
 def attn_shapes_ok(J: int, dm: int, rot: int = 0) -> bool:
@@ -182,14 +192,16 @@ def radial_ok(x, mid_dim: int, eps0: float = 1e-5, eps3: float = 1e-5) -> bool:
 
 def ubuild_ok(B, C, O, I, F) -> bool:
     return (B.is_cuda and B.dtype == torch.float32
-            and C % 32 == 0 and O * I * F <= 343
+            and C >= 1 and O * I * F <= 343
             and not switch_on('SE3_EAGER_UBUILD') and ext_available())
 
 
 def recompute_u_ok(x_nodes, B, C, O, I, F) -> bool:
     """SE3_RECOMPUTE_U: the pair builds U from node features (N, C, I) and
-    edge rows, and builds it again in backward instead of saving it."""
+    edge rows, and builds it again in backward instead of saving it. The
+    gather kernels take C % 32 == 0 only: other pairs keep the saved U."""
     return (x_nodes.is_cuda and x_nodes.dtype in _KERNEL_DTYPES
+            and C % 32 == 0
             and switch_on('SE3_RECOMPUTE_U') and ubuild_ok(B, C, O, I, F))
 
 
@@ -244,19 +256,49 @@ def knn_graph(*args):
     _load_ext().knn_graph(*args)
 
 
+def _pad_rows(W, mo, miF):
+    """W (mo*miF, ...) -> (mo_p*miF_p, ...) with zero rows outside the true
+    (mo, miF); W itself where nothing is to pad."""
+    mo_p, miF_p = pad_dims(mo, miF)
+    if (mo_p, miF_p) == (mo, miF):
+        return W
+    Wp = W.new_zeros(mo_p, miF_p, *W.shape[1:])
+    Wp[:mo, :miF] = W.view(mo, miF, *W.shape[1:])
+    return Wp.view(mo_p * miF_p, *W.shape[1:])
+
+
 def _pack_w_fwd(W16, mo, miF):
     """Rearrange W (mo*miF, 128) bf16 into the forward/du kernels' per-lane
-    fragment order [mo/8][miF/32][wm4][mf4][kit4][lane64][j8] so each wave's
-    MFMA A-fragment load is one contiguous 1 KiB read."""
-    v = W16.view(mo // 8, 4, 2, miF // 32, 2, 16, 4, 4, 8)
+    fragment order [mo_p/8][miF_p/32][wm4][mf4][kit4][lane64][j8] so each
+    wave's MFMA A-fragment load is one contiguous 1 KiB read. Rows outside
+    the true (mo, miF) are zero."""
+    mo_p, miF_p = pad_dims(mo, miF)
+    v = _pad_rows(W16, mo, miF) \
+        .view(mo_p // 8, 4, 2, miF_p // 32, 2, 16, 4, 4, 8)
     return v.permute(0, 3, 1, 2, 4, 6, 7, 5, 8).contiguous()
 
 
 def _pack_w_dh(W16, mo, miF):
     """Fragment order for the dH kernel's B-operand:
-    [mo/8][miF/32][wk2][kf4][ns8][lane64][j8]."""
-    v = W16.view(mo // 8, 8, miF // 32, 4, 8, 2, 4, 16)
+    [mo_p/8][miF_p/32][wk2][kf4][ns8][lane64][j8], zero outside (mo, miF)."""
+    mo_p, miF_p = pad_dims(mo, miF)
+    v = _pad_rows(W16, mo, miF) \
+        .view(mo_p // 8, 8, miF_p // 32, 4, 8, 2, 4, 16)
     return v.permute(0, 2, 5, 6, 1, 3, 7, 4).contiguous()
+
+
+def _pad_u_rows(U, miF):
+    """U (miF or miF_p, E, OP) -> (miF_p, E, OP): a U that already has the
+    padded rows is trusted to hold zeros there (ubuild_opad writes them)."""
+    miF_p = pad_dims(1, miF)[1]
+    if U.shape[0] == miF_p:
+        return U
+    if U.shape[0] != miF:
+        raise ValueError(f'U has {U.shape[0]} rows, W implies {miF} '
+                         f'(or {miF_p} with zero pad rows)')
+    Up = U.new_zeros(miF_p, *U.shape[1:])
+    Up[:miF] = U
+    return Up
 
 
 def opad(O: int) -> int:
@@ -275,38 +317,51 @@ class _FusedPairConvOpad(torch.autograd.Function):
 
     H (E,128) bf16 | W (mo*miF,128) fp32/bf16 param | bias (mo*miF,) fp32
     U (miF,E,OP) bf16, pad lanes o in [O, OP) exactly zero | returns
-    (E, mo, O) fp32. The gradient of U comes back (miF,E,OP) with zero
-    pads, in bf16 (the du kernel rounds its fp32 sums once, as autograd's
-    cast to U's dtype did) or in fp32 with SE3_TORCH_BWD. The kernels
+    (E, mo, O) fp32. Any mo, miF >= 1 (miF is W's, rows / mo): U may also
+    come with ceil32(miF) rows, the pad rows exactly zero (as ubuild_opad
+    writes it), and is padded here otherwise. The gradient of U comes back
+    with the rows and pads of U as passed, in bf16 (the du kernel rounds its
+    fp32 sums once, as autograd's cast to U's dtype did) or in fp32 with
+    SE3_TORCH_BWD. The kernels
     contract whole padded vectors and the bias term's library GEMM reads U
     as a (miF, E*OP) matrix: both rely on the zero pads.
     """
 
     @staticmethod
     def forward(ctx, H, W, bias, U, mo, O):
-        U16 = U.contiguous().to(torch.bfloat16)
+        U16 = _pad_u_rows(U.contiguous().to(torch.bfloat16), W.shape[0] // mo)
         out, H16, wsave, b16 = _pairconv_forward(ctx, H, W, bias, U16, mo, O)
         ctx.save_for_backward(H16, *wsave, U16, b16)
+        ctx.u_rows = U.shape[0]
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         H16, *wsave, U16, b16 = ctx.saved_tensors
-        return (*_pairconv_backward(ctx, H16, wsave, b16, U16, grad_out,
-                                    ctx.needs_input_grad[:4]), None, None)
+        dH, dW, db, dU = _pairconv_backward(ctx, H16, wsave, b16, U16, grad_out,
+                                            ctx.needs_input_grad[:4])
+        if dU is not None:
+            dU = dU[:ctx.u_rows]
+        return dH, dW, db, dU, None, None
 
 
 def _pairconv_forward(ctx, H, W, bias, U16, mo, O):
-    """The forward of both pairconv Functions on U16 (miF, E, OP) bf16.
-    Returns out and what the backward needs besides U: H16, wsave (both
-    fragment packs of W, or W16 alone: ctx.packed says which) and b16."""
+    """The forward of both pairconv Functions on U16 (miF_p, E, OP) bf16,
+    rows >= miF zero. Returns out (E, mo, O) and what the backward needs
+    besides U: H16, wsave (both fragment packs of W, sized for the padded
+    dims, or W16 alone: ctx.packed says which) and b16 (mo, miF)."""
     ext = _load_ext()
     E = H.shape[0]
-    miF, _, OP = U16.shape
+    miF = W.shape[0] // mo
+    mo_p, miF_p = pad_dims(mo, miF)
+    OP = U16.shape[2]
+    if W.shape[0] != mo * miF or U16.shape[0] != miF_p:
+        raise ValueError(f'W {tuple(W.shape)} and U {tuple(U16.shape)} do not '
+                         f'fit mo={mo}')
     H16 = H.contiguous().to(torch.bfloat16)
-    # bias term: out0[e,mo,o] = sum_c bias[mo,c] U[c,e,o]
+    # bias term: out0[e,mo,o] = sum_c bias[mo,c] U[c,e,o], on the true rows
     b16 = bias.detach().to(torch.bfloat16).view(mo, miF)
-    out = (b16 @ U16.view(miF, E * OP)).view(mo, E, OP)[:, :, :O] \
+    out = (b16 @ U16[:miF].view(miF, E * OP)).view(mo, E, OP)[:, :, :O] \
         .permute(1, 0, 2).contiguous().float()
     hip_bwd = not switch_on('SE3_TORCH_BWD')
     # SE3_LOWMEM_PACK=1 trades ~6% step time for memory: save the
@@ -319,16 +374,16 @@ def _pairconv_forward(ctx, H, W, bias, U16, mo, O):
         # one-pass pack kernel: W read once, both fragment layouts
         # written; saved for backward so nothing re-packs per step
         Wd = W.detach().contiguous()
-        n128 = mo * miF * 128
+        n128 = mo_p * miF_p * 128
         Pf = torch.empty(n128, dtype=torch.bfloat16, device=Wd.device)
         Pdh = torch.empty(n128, dtype=torch.bfloat16, device=Wd.device)
-        ext.pack_w_both(Wd, Pf, Pdh, mo)
-        ext.pairconv_fwd_opad(H16, Pf, U16, out, mo)
+        ext.pack_w_both(Wd, Pf, Pdh, mo)    # pad rows written as zeros
+        ext.pairconv_fwd_opad(H16, Pf, U16, out, mo_p)
         wsave = (Pf, Pdh)
         ctx.packed = True
     else:
         W16 = W.detach().contiguous().to(torch.bfloat16)
-        ext.pairconv_fwd_opad(H16, _pack_w_fwd(W16, mo, miF), U16, out, mo)
+        ext.pairconv_fwd_opad(H16, _pack_w_fwd(W16, mo, miF), U16, out, mo_p)
         wsave = (W16,)
         ctx.packed = False
     ctx.mo = mo
@@ -347,7 +402,9 @@ def _pairconv_backward(ctx, H16, wsave, b16, U16, grad_out, needs):
     else:
         W16, = wsave
     E, K = H16.shape
-    miF, _, OP = U16.shape
+    miF = b16.shape[1]
+    mo_p, miF_p = pad_dims(mo, miF)
+    OP = U16.shape[2]
     g = grad_out.contiguous().float()              # (E, mo, O) fp32
 
     need_H, need_W, need_b, need_u = needs
@@ -355,8 +412,9 @@ def _pairconv_backward(ctx, H16, wsave, b16, U16, grad_out, needs):
     ext = _load_ext()
     if not switch_on('SE3_TORCH_BWD'):
         dH = dW = db = dU = None
-        # one pass: cast, transpose and pad, (mo, E, OP) bf16
-        G = torch.empty(mo, E, OP, dtype=torch.bfloat16, device=g.device)
+        # one pass: cast, transpose and pad, (mo_p, E, OP) bf16, rows >= mo
+        # written as zeros
+        G = torch.empty(mo_p, E, OP, dtype=torch.bfloat16, device=g.device)
         ext.pack_g(g, G)
         P1 = Pu = None
         if ctx.packed:
@@ -364,40 +422,42 @@ def _pairconv_backward(ctx, H16, wsave, b16, U16, grad_out, needs):
         elif need_H or need_u:
             # SE3_LOWMEM_PACK path: re-derive both fragment layouts in
             # one kernel pass from the saved torch-layout W
-            n128 = mo * miF * K
+            n128 = mo_p * miF_p * K
             Pu = torch.empty(n128, dtype=torch.bfloat16,
                              device=H16.device)
             P1 = torch.empty_like(Pu)
             ext.pack_w_both(W16, Pu, P1, mo)
         if need_H:
             dH = torch.zeros(E, K, dtype=torch.float32, device=H16.device)
-            ext.pairconv_bwd_dh(G, U16, P1, dH, mo, O)
+            ext.pairconv_bwd_dh(G, U16, P1, dH, mo_p, O)
         P1 = None
         if need_W or need_b:
             # db[(m,c)] = sum_e dR[e,(m,c)]: the dw kernel sums the fp32 dR
             # entries it builds anyway (an empty db: not wanted)
             Ht = H16.t().contiguous()              # (128, E)
-            dW = torch.empty(mo * miF, K, dtype=torch.float32,
+            # 3-D: the true sizes, which the kernel guards its stores by
+            dW = torch.empty(mo, miF, K, dtype=torch.float32,
                              device=H16.device)
             db = torch.empty(mo * miF if need_b else 0, dtype=torch.float32,
                              device=H16.device)
-            ext.pairconv_bwd_dw(G, U16, Ht, dW, db, mo, O)
-            dW = dW.to(ctx.w_dtype) if need_W else None
+            ext.pairconv_bwd_dw(G, U16, Ht, dW, db, mo_p, O)
+            dW = dW.view(mo * miF, K).to(ctx.w_dtype) if need_W else None
             db = db.to(ctx.b_dtype) if need_b else None
             del Ht
         if need_u:
             # bf16 as U: the kernel rounds its fp32 sums once
-            dU = torch.empty(miF, E, OP, dtype=torch.bfloat16,
+            dU = torch.empty(miF_p, E, OP, dtype=torch.bfloat16,
                              device=H16.device)
-            ext.pairconv_bwd_du(H16, Pu, b16.float().reshape(-1),
-                                G, dU, mo, O)
+            ext.pairconv_bwd_du(H16, Pu, _pad_rows(b16.float().reshape(-1),
+                                                   mo, miF),
+                                G, dU, mo_p, O)
         return dH, dW, db, dU
 
     if ctx.packed:   # pragma: no cover - env toggled between fwd and bwd
         raise RuntimeError('SE3_TORCH_BWD enabled after a packed forward; '
                            'set it before the forward pass')
     g16 = g.to(torch.bfloat16)
-    u_eco = U16[:, :, :O].permute(1, 0, 2)         # (E, miF, O) view
+    u_eco = U16[:miF, :, :O].permute(1, 0, 2)      # (E, miF, O) view
     dH = dW = db = dU = None
     if need_H:
         dH = torch.zeros(E, K, dtype=torch.float32, device=H16.device)
@@ -406,7 +466,7 @@ def _pairconv_backward(ctx, H16, wsave, b16, U16, grad_out, needs):
     if need_b:
         db = torch.empty(mo * miF, dtype=torch.float32, device=H16.device)
     if need_u:
-        dU = torch.zeros(miF, E, OP, dtype=torch.float32, device=H16.device)
+        dU = torch.zeros(miF_p, E, OP, dtype=torch.float32, device=H16.device)
 
     # chunk over mo so the dR slab stays ~<= 1 GiB
     per_mo = E * miF * 2
@@ -427,7 +487,7 @@ def _pairconv_backward(ctx, H16, wsave, b16, U16, grad_out, needs):
             # R[e,(m,c)] = H @ W^T + bias ; du[c,e,o] += sum_m R * g
             R = (H16 @ Wslab.t()).view(E, m1 - m0, miF).float() \
                 + b16[m0:m1].float().unsqueeze(0)
-            dU[:, :, :O] += torch.einsum('emc,emo->ceo', R, g[:, m0:m1])
+            dU[:miF, :, :O] += torch.einsum('emc,emo->ceo', R, g[:, m0:m1])
         del dR16
 
     if need_W:
@@ -439,9 +499,16 @@ def _pairconv_backward(ctx, H16, wsave, b16, U16, grad_out, needs):
 
 def fused_pairconv_opad(H, W, bias, U, mo, O=None):
     """Pairwise convolution on U in the o-padded edge-major layout
-    (miF, E, OP(O)) with zero pads; returns (E, mo, O) and differentiates to
-    dU in the same padded shape. O may be omitted where OP decides it
-    (OP 1 -> O 1, OP 4 -> O 3); OP 8 serves O 5 and 7, so say which."""
+    (miF, E, OP(O)) with zero pads, for any mo, miF >= 1 (miF = W rows / mo);
+    returns (E, mo, O) and differentiates to dU in the shape of U.
+
+    U may instead carry ceil32(miF) rows, as ubuild_opad returns it. The pad
+    rows [miF, ceil32(miF)) must then be EXACTLY ZERO, like the pad lanes:
+    they are not checked (that would cost a pass over U and a host sync per
+    call), the forward, dh and dw kernels contract them as they stand, and
+    anything else there gives a wrong out, dH and dW without an error. Pass
+    U with its miF true rows to have the pads made here. O may be omitted where OP decides
+    it (OP 1 -> O 1, OP 4 -> O 3); OP 8 serves O 5 and 7, so say which."""
     OP = U.shape[2]
     if O is None:
         if OP == 8:
@@ -601,9 +668,9 @@ def fused_attention(q, k, v, mask_u8, n, heads, scale, kv_one=False,
 class _UBuildFn(torch.autograd.Function):
     """Basis-feature precontraction (csrc/ubuild.hip):
     U[(c f), e, o] = sum_i B[e,o,i,f] x[e,c,i], emitted directly in the
-    o-padded edge-major layout (C*F, E, OP) the pairconv kernels consume,
-    pad lanes zero. When the basis requires grad (differentiable_coors) x
-    is saved too and backward also returns
+    o-padded edge-major layout (miF_p, E, OP), miF_p = ceil32(C*F), the
+    pairconv kernels consume, pad lanes and the pad rows [C*F, miF_p) zero.
+    When the basis requires grad (differentiable_coors) x is saved too and backward also returns
     dB[e,o,i,f] = sum_c x[e,c,i] dU[(c f),e,o] in fp32, straight-through
     for the forward's bf16 rounding. First order only."""
 
@@ -611,8 +678,9 @@ class _UBuildFn(torch.autograd.Function):
     def forward(ctx, x, B, O, I, F):
         ext = _load_ext()
         E, C, _ = x.shape
-        U = torch.empty(C * F, E, opad(O), dtype=torch.bfloat16,
-                        device=x.device)
+        # ceil32(C*F) rows: the kernel writes the pad rows as zeros
+        U = torch.empty(pad_dims(1, C * F)[1], E, opad(O),
+                        dtype=torch.bfloat16, device=x.device)
         xc = x.contiguous()
         ext.ubuild_fwd(B, xc, U, O, I, F)
         if ctx.needs_input_grad[1]:
@@ -628,7 +696,7 @@ class _UBuildFn(torch.autograd.Function):
         ext = _load_ext()
         B = ctx.saved_tensors[0]
         dtype, (E, C, I_), O, I, F = ctx.meta
-        dU = dU.contiguous()       # (C*F, E, OP), bf16 as U: read as is
+        dU = dU.contiguous()       # (ceil32(C*F), E, OP), bf16 as U: read as is
         dX = dB = None
         if ctx.needs_input_grad[0]:
             dX = torch.empty(E, C, I, dtype=dtype, device=B.device)
@@ -640,13 +708,14 @@ class _UBuildFn(torch.autograd.Function):
 
 
 def ubuild_opad(x, B, O, I, F):
-    """U (C*F, E, OP(O)) bf16, zero pads: what fused_pairconv_opad reads."""
+    """U (ceil32(C*F), E, OP(O)) bf16, zero pad lanes and pad rows: what
+    fused_pairconv_opad reads."""
     return _UBuildFn.apply(x, B, O, I, F)
 
 
 def ubuild(x, B, O, I, F):
     """The e-contiguous (C*F, O, E) contract, as a view of ubuild_opad."""
-    return ubuild_opad(x, B, O, I, F)[:, :, :O].permute(0, 2, 1)
+    return ubuild_opad(x, B, O, I, F)[:x.shape[1] * F, :, :O].permute(0, 2, 1)
 
 
 def edge_rows(neighbor_indices, n: int):
